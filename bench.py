@@ -9,6 +9,11 @@ exchanged with ONE all_gather (RCCL) at the end; the value is the whole-job aggr
     python bench.py [--gpus N] [--steps K] [--warmup W]          # N > 1: starts its own N rank processes
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
     python bench.py --mode video --gpus N --frames 300            # BASELINE config 4: one 300-frame clip per GPU
+
+A plain run sets up, warms up, times the K steps and prints the headline line.  `--full` adds everything else the line
+used to carry (rooflines, HBM-bound kernel timings, secondary sizes / configurations, clips per GPU, the CPU baseline).
+`--dump-outputs DIR` writes the state the last timed step leaves behind as DIR/<name>.npy (float32), so that two builds
+can be compared output for output on the same seeded inputs.
 """
 
 import argparse
@@ -910,6 +915,23 @@ def iteration_roofline(graph, E, n_kf, P, steps_per_s, device):
                     "gate-context convolution hoisted out of the iteration (computed once per edge)"}
 
 
+NET_SAMPLE = 1 << 20  # hidden-state elements kept by --dump-outputs (the whole state is ~0.4 GB in float32)
+
+
+def dump_outputs(out_dir, buf, graph, n_kf):
+    """--dump-outputs: what a caller of FactorGraph.update holds after the last timed step - the keyframe poses and
+    disparities the BA wrote, the flow targets / confidence weights and the damping the operator wrote, and the hidden
+    state the next step starts from (a fixed, seeded sample of it).  float32, ~18 MB at the headline size."""
+    os.makedirs(out_dir, exist_ok=True)
+    V = buf.n_views
+    net = graph.net_n.reshape(-1)
+    pick = torch.randint(net.numel(), (min(NET_SAMPLE, net.numel()),), generator=torch.Generator().manual_seed(0))
+    arrays = {"poses": buf.poses[:n_kf], "disps": buf.disps[:n_kf], "target": graph.target, "weight": graph.weight,
+              "damping": graph.damping[:n_kf * V], "net_sample": net[pick.to(net.device)]}
+    for name, t in arrays.items():
+        np.save(os.path.join(out_dir, f"{name}.npy"), t.detach().float().cpu().numpy())
+
+
 # ---------------------------------------------------------------------------------------------- headline
 def update_mode(args, D):
     from vipe_amd.driver.clip_shard import ClipResult, gather_results
@@ -972,26 +994,30 @@ def update_mode(args, D):
                   and torch.isfinite(graph.target).all())
     n_seen = D.n_ranks_seen()
     _log(f"timed region done: {world * args.steps / dt:.1f} it/s")
+    if args.dump_outputs and rank == 0:  # before anything below runs more steps on the same state
+        dump_outputs(args.dump_outputs, buf, graph, args.keyframes)
+        _log(f"outputs written to {args.dump_outputs}")
 
-    gate_ms, flops_per_launch, achieved, launches_per_step = conv_roofline(graph, step, device, args.prof_steps)
+    if args.full:
+        gate_ms, flops_per_launch, achieved, launches_per_step = conv_roofline(graph, step, device, args.prof_steps)
 
-    # HBM traffic of the dominant kernel per launch: FETCH_SIZE x2 + WRITE_SIZE from the builder's own rocprofv3 --pmc
-    # passes of this command (profiles/rNN_summary.json, committed) - counters cannot be collected from inside the
-    # timed process, so this is NOT a measurement of this run
-    traffic, traffic_src = profile_traffic(("r03_summary.json", "r02_summary.json", "r01_summary.json"), False)
+        # HBM traffic of the dominant kernel per launch: FETCH_SIZE x2 + WRITE_SIZE from the builder's own rocprofv3 --pmc
+        # passes of this command (profiles/rNN_summary.json, committed) - counters cannot be collected from inside the
+        # timed process, so this is NOT a measurement of this run
+        traffic, traffic_src = profile_traffic(("r03_summary.json", "r02_summary.json", "r01_summary.json"), False)
 
-    # matrix-core utilisation of the same kernel from the builder's SQ_VALU_MFMA_BUSY_CYCLES / GRBM_GUI_ACTIVE pass
-    # (profiles/r03_mfma_util.json) - like `traffic`, evidence collected beside this run, not by it
-    mfma_pmc = None
-    for name in ("r03_mfma_util.json", "r02_mfma_util.json"):
-        try:
-            mu = json.load(open(os.path.join(ROOT, "profiles", name)))
-            mu = mu.get("void conv_halo32_kernel<128, 3, true, 0, false>") or mu["void conv_halo32_kernel<128, 3, true, 0>"]
-            mfma_pmc = {"mfma_busy_frac": mu["mfma_util"], "effective_clock_GHz": mu["effective_clock_GHz"],
-                        "avg_launch_ms": mu["avg_us"] / 1e3, "source": f"profiles/{name} (builder-side --pmc pass)"}
-            break
-        except Exception:  # noqa: BLE001
-            pass
+        # matrix-core utilisation of the same kernel from the builder's SQ_VALU_MFMA_BUSY_CYCLES / GRBM_GUI_ACTIVE pass
+        # (profiles/r03_mfma_util.json) - like `traffic`, evidence collected beside this run, not by it
+        mfma_pmc = None
+        for name in ("r03_mfma_util.json", "r02_mfma_util.json"):
+            try:
+                mu = json.load(open(os.path.join(ROOT, "profiles", name)))
+                mu = mu.get("void conv_halo32_kernel<128, 3, true, 0, false>") or mu["void conv_halo32_kernel<128, 3, true, 0>"]
+                mfma_pmc = {"mfma_busy_frac": mu["mfma_util"], "effective_clock_GHz": mu["effective_clock_GHz"],
+                            "avg_launch_ms": mu["avg_us"] / 1e3, "source": f"profiles/{name} (builder-side --pmc pass)"}
+                break
+            except Exception:  # noqa: BLE001
+                pass
 
     if rank == 0:
         out = {
@@ -1022,28 +1048,30 @@ def update_mode(args, D):
                        "gate_context": "context-feature part of the GRU gates computed once per edge (at add_factors, "
                                        "like the correlation volume), not per iteration"
                                        if getattr(graph, "pgate", None) is not None else "recomputed every iteration"},
-            "roofline": {"bound": "mfma", "achieved": achieved, "peak": PEAK_FP16_TFLOPS, "unit": "TFLOP/s",
-                         "frac": achieved / PEAK_FP16_TFLOPS, "traffic": traffic, "traffic_source": traffic_src,
-                         "kernel": "conv_halo32_kernel<128, 3, true, 0> (NHWC fp16 implicit-GEMM 3x3 conv on MFMA 16x16x32: the "
-                                   "launches with Cout >= 128 of the flow-update operator on the main stream, except the "
-                                   "z|r convolution that starts from staged fp32 partial sums = instantiation <..., 1>)",
-                         "avg_launch_ms": gate_ms, "flops_per_launch": flops_per_launch,
-                         "launches_per_step": launches_per_step, "pmc": mfma_pmc},
-            # the whole update iteration against both nominal peaks (SURVEY 8d totals per edge; N source nodes add
-            # 1.37 GFLOP each): MFMA-bound by construction, the HBM figure is what north_star asks to see beside it
-            "iteration_roofline": iteration_roofline(graph, E, args.keyframes, g.ht * g.wd, args.steps / dt / world, device),
         }
-        if world == 1:
+        if args.full:
+            out["roofline"] = {"bound": "mfma", "achieved": achieved, "peak": PEAK_FP16_TFLOPS, "unit": "TFLOP/s",
+                               "frac": achieved / PEAK_FP16_TFLOPS, "traffic": traffic, "traffic_source": traffic_src,
+                               "kernel": "conv_halo32_kernel<128, 3, true, 0> (NHWC fp16 implicit-GEMM 3x3 conv on MFMA 16x16x32: "
+                                         "the launches with Cout >= 128 of the flow-update operator on the main stream, except "
+                                         "the z|r convolution that starts from staged fp32 partial sums = instantiation <..., 1>)",
+                               "avg_launch_ms": gate_ms, "flops_per_launch": flops_per_launch,
+                               "launches_per_step": launches_per_step, "pmc": mfma_pmc}
+        # the whole update iteration against both nominal peaks (SURVEY 8d totals per edge; N source nodes add
+        # 1.37 GFLOP each): MFMA-bound by construction, the HBM figure is what north_star asks to see beside it.  Plain
+        # arithmetic on the timed figure - no run of its own
+        out["iteration_roofline"] = iteration_roofline(graph, E, args.keyframes, g.ht * g.wd, args.steps / dt / world, device)
+        if args.full and world == 1:
             try:
                 out["roofline_hbm_kernels"] = hbm_kernel_rooflines(graph, step, device)
             except Exception as e:  # noqa: BLE001
                 out["roofline_hbm_kernels"] = f"failed: {type(e).__name__}: {e}"
             _log("HBM-bound kernels timed")
-        if world == 1 and not args.no_secondary:
+        if args.full and world == 1 and not args.no_secondary:
             out.update(secondary_figures(args, device, graph, step, out["value"] * E * g.ht * g.wd))
             if isinstance(out.get("frames_per_s"), dict):
                 out["frames_per_s"]["clips_per_gpu"] = args.kclips
-        out["cpu_baseline"] = cpu_baseline() if (world == 1 and not args.no_cpu_baseline) else None
+        out["cpu_baseline"] = cpu_baseline() if (args.full and world == 1 and not args.no_cpu_baseline) else None
         print(json.dumps(out))
     D.close()
     if not finite:
@@ -1059,10 +1087,17 @@ def main():
     ap.add_argument("--height", type=int, default=384, help="update mode: image height (default: the headline's 384)")
     ap.add_argument("--width", type=int, default=512, help="update mode: image width (328 x 584 = the 41 x 73 grid of 16:9 video)")
     ap.add_argument("--extra-edges", type=int, default=0, help="seeded long-range edges on top of the radius-3 graph")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="update mode: after the headline also measure the rooflines, the HBM-bound kernels, the secondary "
+                         "figures, clips per GPU and the CPU baseline (a plain run measures the headline only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="update mode: write the state the last timed step leaves (poses, disparities, targets, weights, "
+                         "damping, a seeded sample of the hidden state) as DIR/<name>.npy in float32")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--no-secondary", action="store_true",
-                    help="update mode: skip the secondary figures (all-gate-work it/s, E=768 it/s, video frames/s)")
-    ap.add_argument("--prof-steps", type=int, default=4)
+                    help="with --full: skip the secondary figures (all-gate-work it/s, E=768 it/s, video frames/s) and "
+                         "clips per GPU")
+    ap.add_argument("--prof-steps", type=int, default=4, help="with --full: event-timed steps of the roofline")
     ap.add_argument("--serial-operator", action="store_true",
                     help="do not use the operator's second stream (vipe_update_buffers.side_stream): for kernel-stats profiles")
     ap.add_argument("--mode", default="update", choices=["update", "video", "backend", "plumbing", "clip-worker", "clips-per-gpu"],
@@ -1087,6 +1122,10 @@ def main():
                     help="video mode: SLAMConfig.pipeline_filter = False (the motion filter of every frame on the main stream, "
                          "strictly before the frontend step)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.dump_outputs and args.mode != "update":
+        ap.error("--dump-outputs is implemented for --mode update only")
 
     launched = "WORLD_SIZE" in os.environ
     if args.gpus > 1 and not launched:
@@ -1100,7 +1139,7 @@ def main():
         print(json.dumps(clips_per_gpu_figure(args)))
         return
     kclips = None
-    if args.mode == "update" and world == 1 and not args.no_secondary:
+    if args.mode == "update" and world == 1 and args.full and not args.no_secondary:
         # K clips per GPU, one process per clip: measured FIRST, while this process has not touched the GPU (its own
         # problems and caches - tens of GB later on - would take the memory two concurrent global BAs need)
         try:

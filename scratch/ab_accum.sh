@@ -5,7 +5,7 @@ cd /tmp && export TMPDIR=/tmp
 for t in "$@"; do
   export VIPE_AMD_LIB=$R/scratch/lib/libvipe_$t.so
   rm -rf /tmp/acc_$t
-  rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/acc_$t -o d -- python3 $R/bench.py --no-cpu-baseline --no-secondary --no-hipgraph --serial-operator > /tmp/acc_$t.log 2>&1
+  rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/acc_$t -o d -- python3 $R/bench.py --full --no-cpu-baseline --no-secondary --no-hipgraph --serial-operator > /tmp/acc_$t.log 2>&1
   python3 - <<PY
 import csv,glob
 f=glob.glob('/tmp/acc_$t/*kernel_stats.csv')[0]

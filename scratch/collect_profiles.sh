@@ -7,14 +7,14 @@ O=$R/gpurun_out/prof
 mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
 PART=${1:-ab}
-B="python3 $R/bench.py --no-cpu-baseline --no-secondary --no-hipgraph --serial-operator"
+B="python3 $R/bench.py --full --no-cpu-baseline --no-secondary --no-hipgraph --serial-operator"
 G="--height 328 --width 584"
 if [[ $PART == *a* ]]; then
 rocprofv3 --kernel-trace --stats --output-format csv -d $O/bench -o b -- $B > $O/bench.log 2>&1
 echo bench stats done
 rocprofv3 --kernel-trace --stats --output-format csv -d $O/bench41 -o b -- $B $G > $O/bench41.log 2>&1
 echo bench 41x73 stats done
-rocprofv3 --kernel-trace --stats --output-format csv -d $O/bench2 -o b -- python3 $R/bench.py --no-cpu-baseline --no-secondary --no-hipgraph > $O/bench2.log 2>&1
+rocprofv3 --kernel-trace --stats --output-format csv -d $O/bench2 -o b -- python3 $R/bench.py --full --no-cpu-baseline --no-secondary --no-hipgraph > $O/bench2.log 2>&1
 echo bench two-stream stats done
 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $O/fetch -o f -- $B > $O/fetch.log 2>&1
 rocprofv3 --pmc WRITE_SIZE --output-format csv -d $O/write -o w -- $B > $O/write.log 2>&1
@@ -41,7 +41,7 @@ unset VIPE_AMD_BACKEND_ALTCORR
 echo backend altcorr done
 rocprofv3 --kernel-trace --stats --output-format csv -d $O/backend -o v -- python3 $R/bench.py --mode backend --steps 5 --warmup 2 > $O/backend.log 2>&1
 echo backend done
-python3 $R/bench.py > $O/bench_line.json 2> $O/bench_line.err
+python3 $R/bench.py --full > $O/bench_line.json 2> $O/bench_line.err
 echo bench line done
 fi
 find $O -name "*_kernel_trace.csv" -delete

@@ -555,8 +555,34 @@ def test_bench_two_ranks_on_one_card_as_a_child_process():
     assert cfg["result_gather"]["backend"] == "gloo" and cfg["launch"].startswith("hipgraph")
 
 
-def test_clips_per_gpu_workers_share_the_card():
-    """`bench.py --mode clips-per-gpu` as the default bench line runs it: a parent that never touches the GPU starts K
+def test_bench_plain_run_times_its_steps_and_dumps_the_last_state(tmp_path):
+    """A plain `bench.py` run (no --full) from a fresh child process: an odd --steps (graph replays + one eager step),
+    the headline line only, and --dump-outputs writing the state of the last timed step in float32 within 64 MB."""
+    import json
+    import os
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    out = tmp_path / "dump"
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
+                        "--keyframes", "10", "--dump-outputs", str(out)],
+                       cwd=root, capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-2000:]
+    line = json.loads([ln for ln in r.stdout.strip().splitlines() if ln.startswith("{")][-1])
+    assert line["steps"] == 3 and line["warmup"] == 1 and line["ms_per_step"] > 0 and line["value"] > 0
+    assert abs(line["ms_per_step"] * line["value"] - 1e3) < 1e-3  # one rank: value = 1000 / ms_per_step
+    assert line["config"]["launch"].startswith("hipgraph") and line["config"]["state_finite"]
+    assert not {"roofline", "roofline_hbm_kernels", "frames_per_s", "value_E768"} & set(line) and line["cpu_baseline"] is None
+    arrays = {f[:-4]: np.load(out / f) for f in os.listdir(out)}
+    assert set(arrays) == {"poses", "disps", "target", "weight", "damping", "net_sample"}
+    assert all(a.dtype == np.float32 and np.isfinite(a).all() for a in arrays.values())
+    assert sum(a.nbytes for a in arrays.values()) <= 64 << 20
+    assert arrays["poses"].shape == (10, 7) and arrays["disps"].shape == (10, 1, 48, 64)
+    assert arrays["target"].shape == arrays["weight"].shape and arrays["target"].shape[2:] == (48, 64, 2)
+
+
+def test_clips_per_gpu_workers_share_the_card(tmp_path):
+    """`bench.py --mode clips-per-gpu` as the `--full` bench line runs it: a parent that never touches the GPU starts K
     clip-worker processes (one `SLAMSystem.run` each: READY -> go -> one JSON line), their global-BA phases take turns on
     the file lock, the trajectories come back through files.  Two workers, short clips: covers the protocol, the lock and
     the release path on a GPU box (no throughput is read off this)."""
@@ -578,9 +604,8 @@ def test_clips_per_gpu_workers_share_the_card():
     assert sum(w is not None and w >= 0 for w in two["backend_lock_wait_seconds"]) == 2  # both workers took the lock
     # a worker with the release path on (what three and more workers per card run)
     env = dict(os.environ)
-    os.makedirs(os.path.join(root, "gpurun_out"), exist_ok=True)
     pr = subprocess.Popen([sys.executable, os.path.join(root, "bench.py"), "--mode", "clip-worker", "--seed", "3", "--frames", "12",
-                           "--height", "128", "--width", "512", "--release-cache", "--share-card", os.path.join(root, "gpurun_out", ".lock_test")],
+                           "--height", "128", "--width", "512", "--release-cache", "--share-card", str(tmp_path / ".lock_test")],
                           stdin=subprocess.PIPE, stdout=subprocess.PIPE, text=True, env=env, cwd=root)
     try:
         assert pr.stdout.readline().strip() == "READY"
