@@ -392,6 +392,27 @@ int vipe_nearest_neighbours(const float* d_query, int qdim, const float* d_tree,
                             float* d_dist, int* d_idx, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * grounding_dino_ext  (csrc/grounding_dino_ext/vision.cpp:9-33, ms_deform_attn_cuda.cu): multi-scale deformable
+ * attention of GroundingDINO's encoder and decoder layers (groundingdino/models/main/ms_deform_attn.py:319-333).
+ *   value [bs,Lv,heads,C], spatial_shapes [L,2] int64 (H, W per level), level_start_index [L] int64,
+ *   sampling_loc [bs,Lq,heads,L,P,2] normalised (x, y), attn_weight [bs,Lq,heads,L,P]; dtype VIPE_F32 or VIPE_F64.
+ * Sample (x W - 0.5, y H - 0.5), bilinear, corners outside the level - or outside [0, Lv) - count as zero: the
+ * reference's multi_scale_deformable_attn_pytorch (ms_deform_attn.py:92-134, grid_sample zeros / align_corners=False).
+ * The whole batch is one launch (the reference's im2col_step chunks do not change the result).  bs * Lq == 0: VIPE_OK,
+ * no launch.  L > 1024 levels: VIPE_EUNSUPPORTED.
+ * ------------------------------------------------------------------------------------------- */
+/* output [bs,Lq,heads*C] (every element written) */
+int vipe_ms_deform_attn_forward(const void* d_value, const int64_t* d_spatial_shapes, const int64_t* d_level_start_index,
+                                const void* d_sampling_loc, const void* d_attn_weight, void* d_output, int64_t bs,
+                                int64_t Lv, int heads, int C, int L, int64_t Lq, int P, int dtype, void* stream);
+/* grad_output [bs,Lq,heads*C] -> grad_value [bs,Lv,heads,C] ACCUMULATED by float atomics (zero it first; last bits
+ * order-dependent), grad_sampling_loc / grad_attn_weight in the shapes of their inputs, written (deterministic). */
+int vipe_ms_deform_attn_backward(const void* d_value, const int64_t* d_spatial_shapes, const int64_t* d_level_start_index,
+                                 const void* d_sampling_loc, const void* d_attn_weight, const void* d_grad_output,
+                                 void* d_grad_value, void* d_grad_sampling_loc, void* d_grad_attn_weight, int64_t bs,
+                                 int64_t Lv, int heads, int C, int L, int64_t Lq, int P, int dtype, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * [fused] flow-update operator convolutions (UpdateModule, droid_net.py:432-499): NHWC fp16
  * implicit-GEMM convolution on MFMA, fp32 accumulate, fused bias + activation.
  *   x [B,H,W,Cin_total] f16, reads channels [cin_off, cin_off+Cin); w packed [KH*KW, Cin, Cout] f16
