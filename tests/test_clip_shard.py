@@ -294,9 +294,8 @@ def test_depth_artifacts_round_trip_and_exr_layout(tmp_path):
 
 
 def test_factor_graph_index_tensors_follow_the_host_mirror():
-    """`FactorGraph.ii / jj / age / ii_inac / jj_inac` are device views of the host mirror made on demand
-    (factor_graph._index_property): edits of the mirror invalidate them, an assignment from outside makes the mirror
-    follow the tensor."""
+    """`FactorGraph.ii / jj / age / ii_inac / jj_inac` are device views of the host arrays (`edge_index.EdgeIndex`) made
+    on demand: an edit of an array invalidates its view and no other, an assignment from outside replaces that array."""
     import numpy as np
     import torch
     from vipe_amd.slam.factor_graph import FactorGraph
@@ -307,13 +306,14 @@ def test_factor_graph_index_tensors_follow_the_host_mirror():
     g.ii_inac = g.jj_inac = torch.zeros(0, dtype=torch.long)
     h = g.host_edges()
     assert h["ii"].tolist() == [3, 4, 5] and h["age"].tolist() == [0, 0, 0] and h["ii_inac"].shape == (0,)
-    h["age"] += 2
-    h["ii"] = np.array([7, 8], dtype=np.int64)
-    h["jj"] = np.array([5, 6], dtype=np.int64)
-    h["age"] = h["age"][:2]
-    g._mirror_changed("ii", "jj", "age")
-    assert g.ii.tolist() == [7, 8] and g.jj.tolist() == [5, 6] and g.age.tolist() == [2, 2]
-    assert g.ii is g.ii  # cached until the mirror changes again
-    g.ii = torch.tensor([1])  # replaced from outside: the mirror is rebuilt from the tensors
+    g._index.tick()
+    g._index.tick()
+    g._index.remove(np.array([True, False, False]), store=False)
+    assert g.ii.tolist() == [4, 5] and g.jj.tolist() == [2, 3] and g.age.tolist() == [2, 2]
+    assert g.ii is g.ii  # cached until the array changes again
+    ii, age = g.ii, g.age
+    g._index.tick()
+    assert g.ii is ii and g.age is not age and g.age.tolist() == [3, 3]  # a tick leaves the views of ii / jj alone
+    g.ii = torch.tensor([1])  # replaced from outside: the host array follows the tensor, a new length restarts the ages
     g.jj = torch.tensor([0])
     assert g.host_edges()["ii"].tolist() == [1] and g.host_edges()["age"].tolist() == [0]

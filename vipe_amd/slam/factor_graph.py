@@ -12,8 +12,9 @@ import os
 import numpy as np
 import torch
 
-from .._lib import check, lib, parse_struct, stream_ptr, upload, upload_many
+from .._lib import check, check_gpu_contig, lib, parse_struct, require, stream_ptr, upload, upload_many
 from ..ext import slam_ext
+from .edge_index import NAMES, EdgeIndex, as_host
 from .networks import AltCorrBlock, CorrBlock, CorrPool
 
 # host-side work counters (edge counts known without touching the device): edges x operator applications, correlation
@@ -42,6 +43,57 @@ def warm_volume_pool(device, gigabytes=None):
 
 RowsJob = parse_struct("vipe_rows_job")   # include/vipe_amd.h
 NhwcJob = parse_struct("vipe_nhwc_job")
+
+
+def per_view(x, V):
+    """edge indices `x` (numpy array or tensor) -> the rows of their V per-view terms: x * V + [0, V)"""
+    if V == 1:
+        return x
+    views = torch.arange(V, device=x.device) if torch.is_tensor(x) else np.arange(V)
+    return (x[:, None] * V + views).reshape(-1)
+
+
+def host_csr(dix, n_src):
+    """`update_engine.segment_csr` on the host (torch.bincount reads its maximum back: a stream drain): the rows grouped
+    by source node `dix` [n] -> int32 (order [n], rowptr [n_src + 1])"""
+    order = np.argsort(dix, kind="stable").astype(np.int32)
+    rowptr = np.concatenate([[0], np.cumsum(np.bincount(dix, minlength=n_src))]).astype(np.int32)
+    return order, rowptr
+
+
+def chunk_groups(cnt, max_edges):
+    """`update_batch`'s chunks, cnt[f] = edges with source frame f.  The reference walks the source keyframes in groups of
+    8 (factor_graph.py:337-343) to bound memory.  The operator couples edges only through GraphAgg's per-source-frame
+    mean, so ANY partition that keeps every source frame's edges together gives the same result: the non-empty groups are
+    merged, in order, while a chunk stays within `max_edges` edges (a single group may exceed it).
+    -> [[first frame of each group of the chunk], ...]"""
+    groups, size = [], 0
+    for g0 in range(0, len(cnt), 8):
+        n8 = int(cnt[g0:g0 + 8].sum())
+        if n8 == 0:
+            continue
+        if not groups or size + n8 > max_edges:
+            groups.append([])
+            size = 0
+        groups[-1].append(g0)
+        size += n8
+    return groups
+
+
+def rows_gather(jobs):
+    """ONE launch of `vipe_rows_gather`: per job (src, dst, idx, n_rows, row_bytes, dst_row0[, seg]) the rows idx[r] of `src`
+    go to the rows dst_row0 + r of `dst` - whole, or with seg = (seg_bytes, seg_pitch, n_seg) that slice per pixel only"""
+    arr = (RowsJob * len(jobs))()
+    for j, job in zip(arr, jobs):
+        src, dst, idx, n_rows, row_bytes, dst_row0, seg = (*job, None)[:7]
+        check_gpu_contig(src, dst, idx)  # their addresses go to the kernel as they are
+        require(idx.dtype == torch.int64, "row indices must be int64")
+        j.src, j.dst, j.idx = src.data_ptr(), dst.data_ptr(), idx.data_ptr()
+        j.src_row_pitch = j.dst_row_pitch = row_bytes
+        j.seg_bytes, j.seg_pitch, j.n_seg = seg or (row_bytes, row_bytes, 1)
+        j.n_rows, j.dst_row0 = int(n_rows), int(dst_row0)
+    if jobs:
+        check(lib().vipe_rows_gather(ctypes.addressof(arr), len(jobs), stream_ptr(jobs[0][2])), "rows_gather")
 
 
 class _EdgeStores:
@@ -108,8 +160,10 @@ class _EdgeStores:
         net_n = self.reserve(n_live + k, net_n, n_live)
         nb = 0 if net_n is None else self.bank_of(net_n)
         P = self.ht * self.wd
+        require(frames.dtype == torch.int64, "frame indices must be int64")
         jobs = (NhwcJob * 2)()
         for j, (src, dst, ctot) in enumerate(((buffer_nets, self.net[nb], 128), (buffer_inps, self.xb[self.cur], 320))):
+            check_gpu_contig(src, frames, dst)  # their addresses go to the kernel as they are
             jobs[j].src, jobs[j].frame, jobs[j].dst = src.data_ptr(), frames.data_ptr(), dst.data_ptr()
             jobs[j].dst_row_pitch, jobs[j].dst_ctot, jobs[j].dst_coff, jobs[j].dst_row0 = P * ctot, ctot, 0, n_live
         check(lib().vipe_gather_nchw_to_nhwc_f16(ctypes.addressof(jobs), 2, k, 128, P, stream_ptr(frames)), "gather_nchw_to_nhwc")
@@ -118,52 +172,30 @@ class _EdgeStores:
 
     def compact(self, keep, n_keep, net_n, extra_jobs=()):
         """rows `keep` [n_keep] int64 (device, ascending) of every store -> the other bank, in ONE launch together with
-        `extra_jobs` = (src, dst, idx, n_rows, row_bytes, dst_row0) of small per-edge arrays; -> (net_n, xbuf, pgate)"""
+        `extra_jobs` (as `rows_gather` takes them) of small per-edge arrays; -> (net_n, xbuf, pgate)"""
         P = self.ht * self.wd
         nb = self.bank_of(net_n)
-        jobs = (RowsJob * 8)()
-        n = 0
-
-        def job(src, dst, idx, n_rows, row_bytes, dst_row0=0, seg=None):
-            nonlocal n
-            j = jobs[n]
-            j.src, j.dst, j.idx = src.data_ptr(), dst.data_ptr(), (idx.data_ptr() if idx is not None else None)
-            j.src_row_pitch = j.dst_row_pitch = row_bytes
-            j.seg_bytes, j.seg_pitch, j.n_seg = seg if seg is not None else (row_bytes, row_bytes, 1)
-            j.n_rows, j.dst_row0 = int(n_rows), int(dst_row0)
-            n += 1
-
+        jobs = []
         if n_keep:
-            job(self.net[nb], self.net[1 - nb], keep, n_keep, P * 128 * 2)
-            job(self.xb[self.cur], self.xb[1 - self.cur], keep, n_keep, P * 320 * 2, seg=(256, 640, P))  # context features only
+            jobs.append((self.net[nb], self.net[1 - nb], keep, n_keep, P * 128 * 2, 0))
+            jobs.append((self.xb[self.cur], self.xb[1 - self.cur], keep, n_keep, P * 320 * 2, 0, (256, 640, P)))  # context features only
             if self.with_pgate:
-                job(self.pg[self.cur], self.pg[1 - self.cur], keep, n_keep, P * 384 * 2)
-        for e in extra_jobs:
-            job(*e)
-        check(lib().vipe_rows_gather(ctypes.addressof(jobs), n, stream_ptr(keep)), "rows_gather")
+                jobs.append((self.pg[self.cur], self.pg[1 - self.cur], keep, n_keep, P * 384 * 2, 0))
+        rows_gather(jobs + list(extra_jobs))
         self.cur ^= 1
         return (self.net[1 - nb][:n_keep], self.xb[self.cur][:n_keep], self.pg[self.cur][:n_keep] if self.with_pgate else None)
 
 
 def _index_property(name):
-    """Device copy of one integer array of the edge bookkeeping (`ii`, `jj`, `age`, `ii_inac`, `jj_inac`): the host mirror
-    (`host_edges`) is what this class works on; the device tensor the reference keeps (factor_graph.py:66-75) is made from
-    it when somebody reads the attribute, and an assignment from outside makes the mirror follow the tensor."""
-    def get(self):
-        dev = self.__dict__.setdefault("_dev", {})
-        t = dev.get(name)
-        if t is None:
-            h = self.__dict__.get("_h")
-            if h is None:
-                return None
-            t = dev[name] = upload(h[name], self.device)
-        return t
+    """One integer array of the edge bookkeeping as the device tensor the reference keeps (factor_graph.py:66-75): made
+    from the host array (`EdgeIndex`, what this class works on) when somebody reads the attribute; an assignment from
+    outside replaces that array."""
+    def put(self, tensor):
+        self._index.assign(name, tensor)
+        if name != "age":
+            self._edges_changed()
 
-    def put(self, value):
-        self.__dict__.setdefault("_dev", {})[name] = value
-        self.__dict__["_h"] = None  # replaced from outside: the mirror is rebuilt from the tensors on next use
-
-    return property(get, put)
+    return property(lambda self: self._index.device(name), put)
 
 
 class FactorGraph:
@@ -176,11 +208,6 @@ class FactorGraph:
         self.cross_view = cross_view and buffer.n_views > 1  # factor_graph.py:62
         ht, wd = buffer.height // 8, buffer.width // 8
         self.ht, self.wd = ht, wd
-        # integer edge bookkeeping: the host mirror is authoritative, `ii` / `jj` / `age` / `ii_inac` / `jj_inac` are device
-        # views of it made on demand (_index_property)
-        z = np.zeros(0, dtype=np.int64)
-        self._h = {"ii": z, "jj": z.copy(), "age": z.copy(), "ii_inac": z.copy(), "jj_inac": z.copy()}
-        self._dev = {}
         self.damping = 1e-6 * torch.ones_like(buffer.flattened_disps)  # factor_graph.py:76
         self.target = torch.zeros([1, 0, ht, wd, 2], device=device, dtype=torch.float)
         self.weight = torch.zeros([1, 0, ht, wd, 2], device=device, dtype=torch.float)
@@ -204,67 +231,40 @@ class FactorGraph:
         self._plan = None
         self._plan_serial = 0   # counts rebuilt edge plans: (serial, kind) identifies the index arrays handed to the BA
         self._ba_state = {}     # private BA workspace + the key of the plan it holds (slam_ext.dense_ba)
+        self._spare = None      # _net_spare's private ping-pong tensor
+        self._inac_cap = None   # backing buffers of target_inac / weight_inac (_inactive_room)
 
-    ii = _index_property("ii")
-    jj = _index_property("jj")
-    age = _index_property("age")  # factor_graph.py:72
-    ii_inac = _index_property("ii_inac")
-    jj_inac = _index_property("jj_inac")
+    ii, jj, age, ii_inac, jj_inac = (_index_property(n) for n in NAMES)  # factor_graph.py:66-75
 
-    def _mirror_changed(self, *names):
-        """the host mirror's arrays `names` were edited: their device copies are stale"""
-        dev = self.__dict__.setdefault("_dev", {})
-        for n in names:
-            dev[n] = None
+    @property
+    def _index(self):
+        """the EdgeIndex, made on first use: tests build bare graphs with `object.__new__` and assign attributes"""
+        index = self.__dict__.get("_edge_index")
+        if index is None:
+            index = self.__dict__["_edge_index"] = EdgeIndex(self.device)
+        return index
 
     def host_edges(self):
-        """Host-side copy of the integer edge bookkeeping {ii, jj, age, ii_inac, jj_inac} (numpy int64) - what every method
-        of this class works on, so that the scheduling logic around the update iteration (duplicate filtering, suppression,
-        age eviction, plan building) reads no device memory back and issues no index arithmetic on the device.  If the
-        attributes were assigned from outside, the mirror is rebuilt from those tensors (one read-back)."""
-        h = self.__dict__.get("_h")
-        if h is None:
-            dev = self.__dict__.setdefault("_dev", {})
-            h = {}
-            for k in ("ii", "jj", "ii_inac", "jj_inac"):
-                t = dev.get(k)
-                h[k] = np.zeros(0, dtype=np.int64) if t is None else t.detach().cpu().numpy().astype(np.int64).copy()
-            t = dev.get("age")
-            h["age"] = (t.detach().cpu().numpy().astype(np.int64).copy() if t is not None and t.shape[0] == h["ii"].shape[0]
-                        else np.zeros_like(h["ii"]))
-            self._h = h
-        return h
+        """The integer edge bookkeeping {ii, jj, age, ii_inac, jj_inac} as the host keeps it (numpy int64, read-only):
+        what every method of this class works on."""
+        return dict(self._index.host)
 
-    def _filter_repeated_edges(self, ii, jj):
-        """factor_graph.py:96-108 on the host mirror (the reference pays a .item() per edge).  ii, jj: numpy."""
-        have = self._edge_set()
-        keep = np.array([(i, j) not in have for i, j in zip(ii.tolist(), jj.tolist())], dtype=bool)
-        return ii[keep], jj[keep]
-
-    def _edge_set(self):
-        """{(i, j)} of all active + inactive edges, kept incrementally (the inactive list grows with the video: rebuilding
-        the set on every call is O(length of the video) of Python per keyframe).  Rebuilt when it is out of step."""
-        h = self.host_edges()
-        n = h["ii"].shape[0] + h["ii_inac"].shape[0]
-        have = getattr(self, "_have", None)
-        if have is None or len(have) != n:
-            have = set(zip(h["ii"].tolist(), h["jj"].tolist())) | set(zip(h["ii_inac"].tolist(), h["jj_inac"].tolist()))
-            self._have = have
-        return have
+    def _edges_changed(self):
+        """the edge set changed: everything derived from it goes - the edge plan with its per-t0 entries, the staged gates"""
+        self._plan = None
+        self._gate_state = None
 
     @torch.no_grad()
     def add_factors(self, ii, jj, remove=False):
         """factor_graph.py:119-173."""
-        ii_h = (ii.detach().cpu().numpy() if torch.is_tensor(ii) else np.asarray(ii)).astype(np.int64).reshape(-1)
-        jj_h = (jj.detach().cpu().numpy() if torch.is_tensor(jj) else np.asarray(jj)).astype(np.int64).reshape(-1)
-        ii_h, jj_h = self._filter_repeated_edges(ii_h, jj_h)
+        ii_h, jj_h = self._index.absent(as_host(ii), as_host(jj))
         if ii_h.shape[0] == 0:
             return
-        if (self.max_factors > 0 and self.host_edges()["ii"].shape[0] + ii_h.shape[0] > self.max_factors and self.corr is not None
+        if (self.max_factors > 0 and self._index.host["ii"].shape[0] + ii_h.shape[0] > self.max_factors and self.corr is not None
                 and remove):
             # factor_graph.py:136-139 (the reference's `arange[argsort(age)]` is the permutation itself; torch's sort
             # leaves the order of equal ages unspecified - the stable order is used here)
-            ix = np.argsort(self.host_edges()["age"], kind="stable")
+            ix = np.argsort(self._index.host["age"], kind="stable")
             self.rm_factors(ix >= self.max_factors - ii_h.shape[0], store=True)
         ii, jj = upload_many([ii_h, jj_h], self.device)
         pi, qi, _, pj, qj, _ = self.buffer.expand_edge_multiview(ii, jj)
@@ -296,15 +296,10 @@ class FactorGraph:
             self.net_n = net if self.net_n is None else torch.cat([self.net_n, net], 0)
         target, _ = self.buffer.reproject_dense_disp(ii, jj)
         target = target[None]
-        h = self.host_edges()
-        self._edge_set().update(zip(ii_h.tolist(), jj_h.tolist()))
-        h["ii"], h["jj"] = np.concatenate([h["ii"], ii_h]), np.concatenate([h["jj"], jj_h])
-        h["age"] = np.concatenate([h["age"], np.zeros_like(ii_h)])
-        self._mirror_changed("ii", "jj", "age")
-        self._gate_state = None
+        self._index.append(ii_h, jj_h)
+        self._edges_changed()
         self.target = torch.cat([self.target, target], 1)
         self.weight = torch.cat([self.weight, torch.zeros_like(target)], 1)
-        self._plan = None
 
     @torch.no_grad()
     def rm_factors(self, mask, store=False):
@@ -312,28 +307,17 @@ class FactorGraph:
         bookkeeping is edited on the host mirror, and the surviving rows of every per-edge tensor - hidden state, context
         features, gate context, targets, weights - and the rows that go to the inactive store move in ONE launch
         (`_EdgeStores.compact`; the reference indexes each tensor with the boolean mask, a sync per tensor)."""
-        m = (mask.detach().cpu().numpy() if torch.is_tensor(mask) else np.asarray(mask)).astype(bool)
+        m = as_host(mask, bool)
         if not m.any():
             return
-        h = self.host_edges()
-        if store:
-            h["ii_inac"] = np.concatenate([h["ii_inac"], h["ii"][m]])
-            h["jj_inac"] = np.concatenate([h["jj_inac"], h["jj"][m]])
-            self._mirror_changed("ii_inac", "jj_inac")
-        elif getattr(self, "_have", None) is not None:
-            self._have.difference_update(zip(h["ii"][m].tolist(), h["jj"][m].tolist()))
-        h["ii"], h["jj"], h["age"] = h["ii"][~m], h["jj"][~m], h["age"][~m]
-        self._mirror_changed("ii", "jj", "age")
+        self._index.remove(m, store)
+        self._edges_changed()
         V = self.buffer.n_views
-        keep_np, drop_np = np.flatnonzero(~m), np.flatnonzero(m)
-        keep_x_np = (keep_np[:, None] * V + np.arange(V)).reshape(-1) if V > 1 else keep_np
-        drop_x_np = (drop_np[:, None] * V + np.arange(V)).reshape(-1) if V > 1 else drop_np
+        keep_x_np, drop_x_np = per_view(np.flatnonzero(~m), V), per_view(np.flatnonzero(m), V)
         keep_x, drop_x = upload_many([keep_x_np, drop_x_np], self.device)
         nk, nd = int(keep_x_np.shape[0]), int(drop_x_np.shape[0])
         if self.corr is not None:
             self.corr = self.corr[keep_x_np]  # host-side index: the pool only edits its slot vector
-        self._gate_state = None
-        self._plan = None
         if not self.target.is_contiguous() or not self.weight.is_contiguous():
             self.target, self.weight = self.target.contiguous(), self.weight.contiguous()
         row = int(self.target.shape[2] * self.target.shape[3] * 2 * 4)  # one edge's [h, w, 2] f32
@@ -353,13 +337,7 @@ class FactorGraph:
         else:  # non-incremental graphs (the backend's): no stores, the small arrays in one launch all the same
             if self.net_n is not None:
                 self.net_n = self.net_n[keep_x]
-            if extra:
-                jobs = (RowsJob * len(extra))()
-                for j, (src, dst, idx, n_rows, rb, r0) in zip(jobs, extra):
-                    j.src, j.dst, j.idx = src.data_ptr(), dst.data_ptr(), idx.data_ptr()
-                    j.src_row_pitch = j.dst_row_pitch = j.seg_bytes = j.seg_pitch = rb
-                    j.n_seg, j.n_rows, j.dst_row0 = 1, int(n_rows), int(r0)
-                check(lib().vipe_rows_gather(ctypes.addressof(jobs), len(extra), stream_ptr(keep_x)), "rows_gather")
+            rows_gather(extra)
         self.target, self.weight = new_t, new_w
 
     def add_neighborhood_factors(self, t0, t1, r=3):
@@ -451,24 +429,13 @@ class FactorGraph:
     def rm_second_newest_keyframe(self, ix):
         """factor_graph.py:204-228: drop keyframe ix (= n_frames - 2) from the buffer and the graph."""
         self.buffer.remove_second_newest(ix)
-        self._have = None  # frame indices shift: the edge set is rebuilt on next use
-        h = self.host_edges()
-        m = (h["ii_inac"] == ix) | (h["jj_inac"] == ix)
-        h["ii_inac"] = h["ii_inac"] - (h["ii_inac"] >= ix)
-        h["jj_inac"] = h["jj_inac"] - (h["jj_inac"] >= ix)
-        if m.any():
-            V = self.buffer.n_views
-            keep = upload(np.flatnonzero(~m), self.device)
-            keep_x = (keep[:, None] * V + torch.arange(V, device=self.device)).view(-1) if V > 1 else keep
+        active, inactive = self._index.drop_keyframe(ix)
+        self._edges_changed()
+        if inactive.any():
+            keep_x = per_view(upload(np.flatnonzero(~inactive), self.device), self.buffer.n_views)
             self.target_inac = self.target_inac[:, keep_x]
             self.weight_inac = self.weight_inac[:, keep_x]
-            h["ii_inac"], h["jj_inac"] = h["ii_inac"][~m], h["jj_inac"][~m]
-        m = (h["ii"] == ix) | (h["jj"] == ix)
-        h["ii"] = h["ii"] - (h["ii"] >= ix)
-        h["jj"] = h["jj"] - (h["jj"] >= ix)
-        self._mirror_changed("ii", "jj", "ii_inac", "jj_inac")
-        self._plan = None
-        self.rm_factors(m, store=False)
+        self.rm_factors(active, store=False)
 
     def get_edges_np(self):
         """factor_graph.py:110-117."""
@@ -492,7 +459,7 @@ class FactorGraph:
         sp = self._stores.net_spare(self.net_n) if self._stores is not None else None
         if sp is not None:
             return sp
-        sp = getattr(self, "_spare", None)
+        sp = self._spare
         if sp is None or sp.shape != self.net_n.shape or sp.data_ptr() == self.net_n.data_ptr():
             sp = torch.empty_like(self.net_n)
         self._spare = self.net_n  # the current state becomes next iteration's spare
@@ -503,28 +470,20 @@ class FactorGraph:
         torch.unique sync, on every update: factor_graph.py:267-268)."""
         if self._plan is None:
             pi, qi, di, pj, qj, _ = self.buffer.expand_edge_multiview(self.ii, self.jj)
-            h = self.host_edges()
-            V = self.buffer.n_views
-            di_h = (h["ii"][:, None] * V + np.arange(V)).reshape(-1)  # = di for edges that are not cross-view self edges
-            if self.cross_view or V > 1:
+            ii_h, jj_h = self._index.host["ii"], self._index.host["jj"]
+            self._plan_serial += 1
+            if self.cross_view or self.buffer.n_views > 1:
+                from .update_engine import segment_csr
                 du, dix = torch.unique(di, return_inverse=True)  # multi-view: take the expansion as computed on the device
                 n_src = int(du.numel())
-            else:
-                du_h, dix_h = np.unique(di_h, return_inverse=True)
+                csr = segment_csr(dix, n_src)
+            else:  # one view: di = ii, everything from the host arrays
+                du_h, dix_h = np.unique(ii_h, return_inverse=True)
                 du, dix = upload_many([du_h, dix_h], self.device)
                 n_src = int(du_h.shape[0])
-            from .update_engine import segment_csr
-            self._plan_serial = getattr(self, "_plan_serial", 0) + 1
-            if self.cross_view or V > 1:
-                csr = segment_csr(dix, n_src)
-            else:  # the same CSR from the host mirror (torch.bincount reads its maximum back: a stream drain)
-                order_h = np.argsort(dix_h, kind="stable").astype(np.int32)
-                rowptr_h = np.concatenate([[0], np.cumsum(np.bincount(dix_h, minlength=n_src))]).astype(np.int32)
-                csr = tuple(upload_many([order_h, rowptr_h], self.device, torch.int32))
-            self._plan = dict(pi=pi, qi=qi, di=di, pj=pj, qj=qj, du=du, dix=dix, n_src=n_src,
-                              csr=csr,
-                              t0=int(max(1, h["ii"].min() + 1)),
-                              t1=int(max(h["ii"].max(), h["jj"].max()) + 1))
+                csr = tuple(upload_many(host_csr(dix_h, n_src), self.device, torch.int32))
+            self._plan = dict(pi=pi, qi=qi, di=di, pj=pj, qj=qj, du=du, dix=dix, n_src=n_src, csr=csr,
+                              t0=int(max(1, ii_h.min() + 1)), t1=int(max(ii_h.max(), jj_h.max()) + 1))
         return self._plan
 
     def _inactive_room(self, k):
@@ -532,7 +491,7 @@ class FactorGraph:
         whole store, on every eviction): backing buffers with spare capacity; -> (target buffer, weight buffer, first
         free row) with room for k more rows, the attributes re-pointed to the n + k rows (the caller fills the new ones)."""
         n = self.target_inac.shape[1]
-        cap = getattr(self, "_inac_cap", None)
+        cap = self._inac_cap
         if cap is None or cap[0].shape[1] < n + k or cap[0].data_ptr() != self.target_inac.data_ptr():
             size = max(2 * (n + k), 256)
             cap = tuple(torch.empty((1, size) + tuple(x.shape[2:]), dtype=x.dtype, device=x.device)
@@ -620,29 +579,25 @@ class FactorGraph:
             # indexing (a device-to-host sync each) and no re-expansion
             key = ("inac", t0)
             if key not in P:
-                h = self.host_edges()
-                sel_h = np.flatnonzero((h["ii_inac"] >= t0 - 3) & (h["jj_inac"] >= t0 - 3))  # host mirror: no read-back
-                # [selected inactive | active] index vectors straight from the host mirror: one staged copy
-                V = buf.n_views
-                sel_x = sel_h if V == 1 else (sel_h[:, None] * V + np.arange(V)).reshape(-1)
+                h = self._index.host
+                sel_h = np.flatnonzero((h["ii_inac"] >= t0 - 3) & (h["jj_inac"] >= t0 - 3))  # host arrays: no read-back
+                # [selected inactive | active] index vectors straight from the host arrays: one staged copy
                 ii, jj, sel_exp = upload_many([np.concatenate([h["ii_inac"][sel_h], h["ii"]]),
-                                               np.concatenate([h["jj_inac"][sel_h], h["jj"]]), sel_x], self.device)
+                                               np.concatenate([h["jj_inac"][sel_h], h["jj"]]),
+                                               per_view(sel_h, buf.n_views)], self.device)
                 base = int(min(h["ii"].min(), h["jj"].min(), *(h[k][sel_h].min() for k in ("ii_inac", "jj_inac") if sel_h.size)))
-                P[key] = (ii, jj, sel_exp, self._shift_plan(buf.expand_edge_multiview(ii, jj)[:5], base))
-            ii, jj, sel_exp, plan = P[key]
-            plan_key = (self._plan_serial, "inac", t0)
-            # [selected inactive | active] targets / weights live in ONE buffer per edge set: the inactive part is
-            # gathered once (it never changes), self.target / self.weight are views of the tail that the iteration
-            # rewrites in place - the reference concatenates both every call (factor_graph.py:300-304)
-            ckey = ("comb", t0)
-            if ckey not in P:
+                plan = self._shift_plan(buf.expand_edge_multiview(ii, jj)[:5], base)
+                # [selected inactive | active] targets / weights live in ONE buffer per edge set: the inactive part is
+                # gathered once (it never changes), self.target / self.weight are views of the tail that the iteration
+                # rewrites in place - the reference concatenates both every call (factor_graph.py:300-304)
                 n_sel = int(sel_exp.shape[0])
                 comb = tuple(torch.empty((1, n_sel + E_act) + tuple(x.shape[2:]), dtype=x.dtype, device=x.device)
                              for x in (self.target, self.weight))
                 comb[0][:, :n_sel] = self.target_inac.index_select(1, sel_exp)
                 comb[1][:, :n_sel] = self.weight_inac.index_select(1, sel_exp)
-                P[ckey] = (comb, n_sel)
-            comb, n_sel = P[ckey]
+                P[key] = (ii, jj, plan, comb, n_sel)
+            ii, jj, plan, comb, n_sel = P[key]
+            plan_key = (self._plan_serial, "inac", t0)
             if self.target.data_ptr() != comb[0][:, n_sel:].data_ptr():
                 comb[0][:, n_sel:] = self.target
                 comb[1][:, n_sel:] = self.weight
@@ -651,20 +606,18 @@ class FactorGraph:
         else:
             ii, jj, target, weight = self.ii, self.jj, self.target, self.weight
             if "ba_plan" not in P:  # cached expand_edge_multiview of the edge set, relative to the oldest keyframe used
-                h = self.host_edges()
                 P["ba_plan"] = self._shift_plan((P["pi"], P["qi"], P["di"], P["pj"], P["qj"]),
-                                                int(min(h["ii"].min(), h["jj"].min())))
+                                                int(min(self._index.host["ii"].min(), self._index.host["jj"].min())))
             plan = P["ba_plan"]
             plan_key = (self._plan_serial, "act")
         E = target.shape[1]
         buf.bundle_adjustment(target.view(E, -1, 2), weight.view(E, -1, 2), self.damping, ii, jj, t0,
                               t1 if not fixed_motion else t0, itrs, 1e-3, 0.1, motion_only, limited_disp, False, False,
-                              plan=plan, ba_state=getattr(self, "_ba_state", None), plan_key=plan_key, overlap=ba_overlap)
+                              plan=plan, ba_state=self._ba_state, plan_key=plan_key, overlap=ba_overlap)
         if overlap:
             main.wait_stream(self._side)
             self._gate_state = gate_state
-        self.host_edges()["age"] += 1  # factor_graph.py:306
-        self._mirror_changed("age")
+        self._index.tick()
 
     @torch.no_grad()
     def update_batch(self, itrs, steps, optimize_intrinsics, optimize_rig_rotation, solver_verbose=False):
@@ -695,13 +648,10 @@ class FactorGraph:
         # ... and when they do not (more than ~4800 edges at 48 x 64: clips of 300+ keyframes), as MANY chunks as fit next
         # to the one being worked on stay resident; the others are rebuilt every pass (8.5 us per edge)
         keep_some = use_volume and steps > 1 and not keep_vols
-        # The reference walks the source keyframes in groups of 8 (factor_graph.py:337-343) to bound memory.  The
-        # operator couples edges only through GraphAgg's per-source-frame mean, so ANY partition that keeps every
-        # source frame's edges together gives the same result: with 288 GB of HBM the groups are merged until a
-        # chunk holds up to VIPE_AMD_BACKEND_CHUNK_EDGES edges (default 4096, ~110 GB of pyramids at 48 x 64) - normally one chunk.
-        # Edge indices come from the host mirror; chunks are selected with index vectors, not masks.
-        h_ = self.host_edges()
-        ii_np, jj_np = h_["ii"], h_["jj"]
+        # With 288 GB of HBM the reference's groups of 8 source keyframes are merged (`chunk_groups`) until a chunk holds up
+        # to VIPE_AMD_BACKEND_CHUNK_EDGES edges (default 4096, ~110 GB of pyramids at 48 x 64) - normally one chunk.
+        # Edge indices come from the host arrays; chunks are selected with index vectors, not masks.
+        ii_np, jj_np = self._index.host["ii"], self._index.host["jj"]
         assert jj_np.max() >= ii_np.max()
         E_all = ii_np.shape[0]
         # a chunk's pyramids must fit the volume budget (VIPE_AMD_BACKEND_VOLUME_GB) whatever the grid: 33 MB per edge at
@@ -712,18 +662,7 @@ class FactorGraph:
         if keep_some:  # finer chunks: one eighth of the budget each, so that seven of eight budget shares can stay resident
             max_edges = max(8, min(max_edges, max(256, budget_rows // (8 * V))))
         cnt = np.bincount(ii_np)
-        groups, cur, cur_n = [], [], 0
-        for g0 in range(0, len(cnt), 8):  # the reference's groups of 8 source frames are the merge unit
-            n8 = int(cnt[g0:g0 + 8].sum())
-            if n8 == 0:
-                continue
-            if cur and cur_n + n8 > max_edges:
-                groups.append(cur)
-                cur, cur_n = [], 0
-            cur.append(g0)
-            cur_n += n8
-        if cur:
-            groups.append(cur)
+        groups = chunk_groups(cnt, max_edges)
         max_rows = max(int(sum(cnt[g0:g0 + 8].sum() for g0 in grp)) for grp in groups) * V  # the largest chunk's pyramids
         # Everything about a chunk that does not change during the `steps` passes is prepared once: index vectors, the
         # source-node CSR, the frame masks, the context features in the operator's input buffer and - like the
@@ -741,17 +680,14 @@ class FactorGraph:
                 c["idx_x"] = None
             else:
                 idx = upload(sel, self.device)
-                c["idx_x"] = (idx[:, None] * V + torch.arange(V, device=self.device)).view(-1) if V > 1 else idx
+                c["idx_x"] = per_view(idx, V)
                 iis, jjs = self.ii[idx], self.jj[idx]
             pis, qis, dis, pjs, qjs, djs = buf.expand_edge_multiview(iis, jjs)
-            dis_np = (ii_np[sel][:, None] * V + np.arange(V)).reshape(-1)
-            du_np, dixs_np = np.unique(dis_np, return_inverse=True)
+            du_np, dixs_np = np.unique(per_view(ii_np[sel], V), return_inverse=True)
             du_d, dixs_d = upload_many([du_np, dixs_np], self.device)
             c.update(pis=pis, qis=qis, dis=dis, pjs=pjs, qjs=qjs, djs=djs, n=sel.shape[0] * V, n_src=int(du_np.shape[0]),
                      du=du_d, dixs=dixs_d, mask=buf.masks[pis, qis].contiguous())
-            order_h = np.argsort(dixs_np, kind="stable").astype(np.int32)
-            rowptr_h = np.concatenate([[0], np.cumsum(np.bincount(dixs_np, minlength=c["n_src"]))]).astype(np.int32)
-            c["csr"] = tuple(upload_many([order_h, rowptr_h], self.device, torch.int32))
+            c["csr"] = tuple(upload_many(host_csr(dixs_np, c["n_src"]), self.device, torch.int32))
             xb = torch.empty((c["n"], self.ht, self.wd, 320), dtype=torch.half, device=self.device)
             xb[..., 0:128] = buf.inps[pis, qis].permute(0, 2, 3, 1)
             c["xb"] = xb
