@@ -178,7 +178,7 @@ def _path_hint(state, key):
         if len(hints) > 64:
             hints.clear()
         degree, solved = int(host[6]), int(host[5])  # solved: 0 global-memory Cholesky, 1 LDS band solver, 2 LDS dense solver
-        if degree > 0:  # AM_DMAX = 6 in csrc/ba.hip: the matrix-core accumulate kernel covers source degrees up to 6
+        if degree > 0:  # AM_DMAX = 6 in csrc/ba_common.cuh: the matrix-core accumulate kernel covers source degrees up to 6
             hints[k] = (1 if degree <= 6 else 2) | {0: 8 | 16, 1: 4 | 16, 2: 4 | 8}.get(solved, 0)
     return hints.get(key, 0)
 
