@@ -98,6 +98,85 @@ def test_flat_tile_two_source_input_and_initial_accumulators():
     assert (y3.float().cpu().permute(0, 3, 1, 2) - full).abs().max().item() < 6e-3
 
 
+def test_gather_kernel_fused_epilogues_against_torch_fp32():
+    """The fused epilogues of the per-tap gather kernels (GLO, ZR, Q, HEADS, ETA): 130 columns fit no tile kernel, so
+    `vipe_conv2d_fused` at (2, 8, 130) takes the gather path with the operator's shapes; 1040 pixels per image also put
+    two images into one 128-pixel tile.  Against a torch fp32 restatement that rounds where the kernel rounds: fp32
+    convolution of the fp16 operands + bias (+ per-image term), activation, round to fp16, blend in fp32, round to fp16.
+    fp16 outputs at the 4e-3 of the plain convolutions above; HEADS / ETA the same bound on the fp16-rounded value
+    (ETA: before its 0.01 factor); the GLO sum within 2^-10 * sum |sigmoid * net| per image and channel (each term
+    may differ by one fp16 step of the sigmoid)."""
+    import torch.nn.functional as F
+    from vipe_amd._lib import check, lib, ptr, stream_ptr
+    from vipe_amd.slam.update_engine import _Packed
+    B, H, W = 2, 8, 130
+    g = torch.Generator().manual_seed(130)
+
+    def rnd(*shape, scale=0.5):
+        return (torch.randn(*shape, generator=g) * scale).half()
+
+    def weights(cout, cin, k):
+        return (torch.randn(cout, cin, k, k, generator=g) / (cin * k * k) ** 0.5).half(), torch.randn(cout, generator=g) * 0.1
+
+    def conv(x, w, b, extra=None, off=0):  # NHWC fp16 in, [B,H,W,cout] fp32 out
+        v = F.conv2d(x.float().permute(0, 3, 1, 2), w.float(), b, padding=w.shape[-1] // 2).permute(0, 2, 3, 1)
+        return v if extra is None else v + extra[:, None, None, off:off + w.shape[0]]
+
+    def h16(t):
+        return t.half().float()
+
+    def ctot(t):
+        return 0 if t is None else t.shape[-1]
+
+    def fused(x0, x1, split, w, b, extra, extra_off, y, y2, net, z, fout, mode):
+        pk = _Packed(w, b, dev())
+        x0d, x1d, exd, yd, y2d, netd, zd, fd = [None if t is None else t.to(dev()) for t in (x0, x1, extra, y, y2, net, z, fout)]
+        check(lib().vipe_conv2d_fused(ptr(x0d), ctot(x0), 0, ptr(x1d), ctot(x1), 0, split, ptr(pk.packed), ptr(pk.bias),
+                                      ptr(exd), ctot(extra), extra_off, ptr(yd), ctot(y), 0, ptr(y2d), ctot(y2), 0,
+                                      ptr(netd), ctot(net), 0, ptr(zd), ptr(fd), None, 0, 0, B, H, W, w.shape[1], w.shape[0],
+                                      w.shape[2], w.shape[3], 0, mode, stream_ptr(x0d)), "conv_fused mode %d" % mode)
+        torch.cuda.synchronize()
+        return [None if t is None else t.float().cpu() for t in (yd, y2d, fd)]
+
+    net = rnd(B, H, W, 128, scale=1.0).float().tanh().half()
+    xb = rnd(B, H, W, 320)
+    extra = torch.randn(B, 384, generator=g) * 0.1
+    out128 = torch.zeros(B, H, W, 128).half()
+    # GLO: sum over the image of sigmoid(w(x) + b) * net, the convolution input being another tensor than `net`
+    x = rnd(B, H, W, 128)
+    w, b = weights(128, 128, 1)
+    _, _, glo = fused(x, None, 128, w, b, None, 0, None, None, net, None, torch.zeros(B, 128), 1)
+    terms = h16(torch.sigmoid(conv(x, w, b))) * net.float()
+    err, bound = (glo - terms.sum((1, 2))).abs(), 2.0 ** -10 * terms.abs().sum((1, 2))
+    assert bool((err <= bound).all()), ("GLO", float((err / bound).max()), float(err.max()))
+    # ZR: z = sigmoid(.)[:128] and r * net from channels [128, 256), two-source input [net | xb]
+    w, b = weights(256, 448, 3)
+    z, rnet, _ = fused(net, xb, 128, w, b, extra, 0, out128, out128, net, None, None, 2)
+    s = h16(torch.sigmoid(conv(torch.cat([net, xb], -1), w, b, extra, 0)))
+    errs = (float((z - s[..., :128]).abs().max()), float((rnet - h16(s[..., 128:] * net.float())).abs().max()))
+    assert max(errs) < 4e-3, ("ZR", errs)
+    # Q: (1 - z) * net + z * tanh(.), two-source input [r * net | xb]
+    zh, rh = z.half(), rnet.half()
+    w, b = weights(128, 448, 3)
+    hnew, _, _ = fused(rh, xb, 128, w, b, extra, 256, out128, None, net, zh, None, 3)
+    q = h16(torch.tanh(conv(torch.cat([rh, xb], -1), w, b, extra, 256)))
+    err = float((hnew - h16((1.0 - zh.float()) * net.float() + zh.float() * q)).abs().max())
+    assert err < 4e-3, ("Q", err)
+    # HEADS: delta, delta, sigmoid, sigmoid as float [M, 4]
+    x = rnd(B, H, W, 256)
+    w, b = weights(4, 256, 3)
+    _, _, heads = fused(x, None, 256, w, b, None, 0, None, None, None, None, torch.zeros(B, H, W, 4), 4)
+    v = conv(x, w, b)
+    err = float((heads - torch.cat([h16(v[..., :2]), h16(torch.sigmoid(v[..., 2:]))], -1)).abs().max())
+    assert err < 4e-3, ("HEADS", err)
+    # ETA: 0.01 * softplus(.) as float [M]
+    x = rnd(B, H, W, 128)
+    w, b = weights(1, 128, 3)
+    _, _, eta = fused(x, None, 128, w, b, None, 0, None, None, None, None, torch.zeros(B, H, W), 5)
+    err = float((eta / 0.01 - h16(F.softplus(conv(x, w, b)[..., 0]))).abs().max())
+    assert err < 4e-3, ("ETA", err)
+
+
 @pytest.mark.parametrize("grid", [(41, 73), (35, 85), (55, 55), (6, 9)])
 def test_update_operator_on_ragged_grids_matches_torch_restatement(grid):
     """The whole flow-update operator (13 fused convolutions, gate-context hoisting, global-context kernel, GraphAgg) on

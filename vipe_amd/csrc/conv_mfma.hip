@@ -362,17 +362,12 @@ __global__ __launch_bounds__(256) void conv_mfma_glds_kernel(ConvArgs a, int gy)
 #include "conv_epilogue.inc"
 }
 
-// ---- Halo-tile variant (image width 64, 1x1 / 3x3): the workgroup (8 waves) owns 4 full image rows (256 pixels)
-// x 128 output channels.  For every 64-channel chunk the (4+2) x (64+2) input halo is brought to LDS ONCE and the
-// 9 taps are read from it as shifted windows, so the L2 -> LDS traffic per FLOP is ~3x lower than with per-tap
-// gathers (the measured limiter: ~70 GB/s per CU of LDS-DMA bandwidth).  Weights stream per (tap, chunk) through a
-// 2 x 16 KB ring; the next chunk's halo is prefetched one 1-KiB piece per wave per tap step.
+// ---- Tile kernels (conv_halo32_kernel, conv_halo32_narrow_kernel, conv7x7_c4_kernel; 512 lanes = 8 waves each): the
+// workgroup owns 4 image rows x 64 pixels = 256 pixels and brings their input halo to LDS once, instead of gathering
+// it per tap (the per-tap kernels are limited by ~70 GB/s per CU of LDS-DMA bandwidth).
 constexpr int HALO_TH = 4, HALO_TW = 64;
 constexpr int HALO_PITCH = HALO_TW + 2;                 // 66
 constexpr int HALO_ROWS = (HALO_TH + 2) * HALO_PITCH;  // 396
-constexpr int HALO_PIECES = (HALO_ROWS + 7) / 8;       // 50
-constexpr int HALO_LDS_ROWS = HALO_PIECES * 8;         // 400
-constexpr int HALO_XP = (HALO_PIECES + 7) / 8;         // pieces per wave (7)
 
 __device__ __forceinline__ void glds16_off(const void* base, unsigned voff_bytes, unsigned lds_addr) {
 #if defined(__HIP_DEVICE_COMPILE__)
@@ -416,28 +411,26 @@ __device__ __forceinline__ void dma16v(uint64_t lane_ptr, unsigned lds_addr) {  
 #endif
 }
 
-// ---- Halo-tile kernel, K step 32: TWO workgroups per CU.
-// Same tile (8 waves: 4 image rows x 64 px x BMC couts) and the same halo idea as above, but the channel chunk is 32
-// (64-byte LDS rows): halo double buffer 2 x 25 KiB + weight ring 3 x 8 KiB = 75 KiB, so two workgroups share a CU
-// (4 waves per SIMD) and one workgroup's prologue / epilogue / barrier stalls are covered by the other's MFMAs
-// (measured on the 64-channel kernel: 12 us of 27..63 us per workgroup were spent outside the K loop with nothing
-// to overlap them).  The epilogue applies bias + activation in the accumulator layout and stages the tile as fp16
-// (69 KiB), then every lane blends / stores 8 consecutive channels of one pixel.
-// LDS rows are 4 chunks of 16 B; logical chunk c of row r sits at slot c ^ ((r >> 2) & 3): the 16-lane groups of a
-// ds_read_b128 (rows r0 + {0..3, 12..15, 20..27}, one logical chunk) then cover 16 distinct 16-byte slots of the
-// 256-byte bank window for every window shift r0.
+// ---- Halo-tile kernel (1x1 / 3x3), K step 32: TWO workgroups per CU.
+// The tile is 4 image rows x 64 px x BMC couts.  For every 32-channel chunk the (4 + 2) x (64 + 2) input halo is
+// brought to LDS ONCE and the 9 taps are read from it as shifted windows, so the L2 -> LDS traffic per FLOP is ~3x
+// lower than with per-tap gathers.  Weights stream per (tap, chunk) through a ring of three slots; the next chunk's
+// halo is prefetched one 1-KiB piece per wave per tap step.  64-byte LDS rows: halo double buffer 2 x 25 KiB + weight
+// ring 3 x 8 KiB = 75 KiB, so two workgroups share a CU (4 waves per SIMD) and one workgroup's prologue / epilogue /
+// barrier stalls are covered by the other's MFMAs (measured on a kernel with 64-channel chunks: 12 us of 27..63 us per
+// workgroup were spent outside the K loop with nothing to overlap them).  The epilogue applies bias + activation in
+// the accumulator layout and stages the tile as fp16 (69 KiB), then every lane blends / stores 8 consecutive channels
+// of one pixel.
 constexpr int H32_PIECES = (HALO_ROWS + 15) / 16;  // 25 one-KiB pieces (16 rows x 64 B) per halo chunk
 constexpr int H32_XBYTES = H32_PIECES * 1024;      // 25600
 constexpr int H32_XP = (H32_PIECES + 7) / 8;       // pieces per wave (4)
 constexpr int H32_BK = 32;
 
-// chunk swizzle of a 64-byte row.  32x32x16 fragments (16-lane read groups = rows r0 + {0..3, 12..15, 20..27}, one
-// logical chunk): c ^ ((r >> 2) & 3).  16x16x32 fragments (read groups = rows r0 + {0..3, 12..15} with chunk kc and
-// rows r0 + {4..11} with chunk kc ^ 1): c ^ 2 * ((r >> 2) & 1) - both cover 16 distinct 16-byte slots for every r0.
-template <bool M16>
-__device__ __forceinline__ int swzf(int row) { return M16 ? ((row >> 2) & 1) << 1 : (row >> 2) & 3; }
-template <bool M16>
-__device__ __forceinline__ int swz32(int row, int c) { return row * 64 + ((c ^ swzf<M16>(row)) << 4); }
+// LDS rows are 4 chunks of 16 B; logical chunk c of row r sits at slot c ^ 2 * ((r >> 2) & 1): the 16-lane groups of a
+// 16x16x32 fragment's ds_read_b128 (rows r0 + {0..3, 12..15} with chunk kc and rows r0 + {4..11} with chunk kc ^ 1)
+// then cover 16 distinct 16-byte slots of the 256-byte bank window for every window shift r0.
+__device__ __forceinline__ int swzf(int row) { return ((row >> 2) & 1) << 1; }
+__device__ __forceinline__ int swz32(int row, int c) { return row * 64 + ((c ^ swzf(row)) << 4); }
 
 
 // position q of a flat tile -> pixel index of image e ((e * H + y) * W + x), or -1 for the pad column / beyond the image
@@ -460,10 +453,12 @@ __device__ __forceinline__ int flat_pixel(int q, int e, int H, int W, int wp, in
 // tiles would run at 53 %.  Wave wn owns positions 64 wn .. 64 wn + 63; pad positions are computed and not stored.
 template <int BMC, int KS, bool M16, int VAR = 0, bool FLAT = false>
 __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4, 4))) void conv_halo32_kernel(ConvArgs a, int gy) {
-  // M16: v_mfma_f32_16x16x32_f16 (one instruction per 32-channel step and 16 x 16 tile; the chip holds a higher
-  // clock on this shape, MI355X_MICROARCH.md 'DVFS give-back' (7)); otherwise 32x32x16.
-  constexpr int TM = BMC >= 128 ? 2 : 1, TN = BMC == 32 ? 1 : 2, BP = HALO_TH * HALO_TW;
-  constexpr int MI = TM * 2, NJ = TN * 2;  // 16 x 16 tiles per wave (M16)
+  // v_mfma_f32_16x16x32_f16: one instruction per 32-channel step and 16 x 16 tile (the chip holds a higher clock on
+  // this shape than on 32x32x16, MI355X_MICROARCH.md 'DVFS give-back' (7)).  M16 selects nothing any more: it stays in
+  // the template head because profiles and benchmark tables are keyed on the kernel's full name.
+  static_assert(M16, "only the 16x16x32 form exists");
+  constexpr int MI = BMC >= 128 ? 4 : 2, NJ = BMC == 32 ? 2 : 4;  // 16 x 16 tiles per wave
+  constexpr int BP = HALO_TH * HALO_TW;
   constexpr int WSTAGE = BMC * 64;  // bytes per weight ring slot
   extern __shared__ __align__(16) unsigned char lds[];
 
@@ -486,7 +481,6 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
   };
   const int cs32 = a.Cin_pad / H32_BK, cs64 = a.Cin_pad / 64;
   const int r16 = lane >> 2, sl = lane & 3;
-  const int lrow = lane & 31, lhalf = lane >> 5;
 
   const unsigned ldsW_a = lds_address(lds), ldsX_a = ldsW_a + 3 * WSTAGE;
   const unsigned sink_a = ldsX_a + 2 * xbytes;  // 1 KiB sink for the count-keeping dummy DMAs
@@ -498,14 +492,14 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
   constexpr int WPIECES = BMC / 16;  // 1-KiB pieces per weight slot: 8 / 4 / 2 -> waves 0..WPIECES-1 carry one each
   const bool wreal = wave < WPIECES;
   const int wrow = (wave % WPIECES) * 16 + r16;
-  const unsigned woff = (unsigned)(wrow * 64 + ((sl ^ swzf<M16>(wrow)) << 3)) * 2u;
+  const unsigned woff = (unsigned)(wrow * 64 + ((sl ^ swzf(wrow)) << 3)) * 2u;
   const unsigned wdst = ldsW_a + (wave % WPIECES) * 1024;
   // halo pieces: one VGPR each (pixel index of this lane's halo row, or -1 outside the image); the lane's channel
   // chunk is the same for every piece because (16 * piece) >> 2 is a multiple of 4
   // FLAT: halo row r holds position q0 - (Wp + 1) + r; its pixel index is recomputed at every issue (4 per wave and
   // chunk, ~15 VALU each) instead of being kept in registers the K loop has none to spare of
   int xpix[FLAT ? 1 : H32_XP];
-  const int xk = (sl ^ swzf<M16>(r16)) * 8;
+  const int xk = (sl ^ swzf(r16)) * 8;
   if constexpr (!FLAT) {
 #pragma unroll
     for (int i = 0; i < H32_XP; ++i) {
@@ -550,14 +544,10 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
   const unsigned tstride = (unsigned)cs64 * (unsigned)a.Cout_pad * BK * 2u;    // bytes from one tap's packed blocks to the next's
   const unsigned sink_u = __builtin_amdgcn_readfirstlane(sink_a), wdst_u = __builtin_amdgcn_readfirstlane(wdst);
   const unsigned ldsX_u = __builtin_amdgcn_readfirstlane(ldsX_a + wave * 1024);
-  auto issueW2 = [&](int tap, int c, int slot, auto ONC, bool more_) {  // weights of K-step (tap, c) into ring slot `slot`
+  auto issueW2 = [&](int tap, int c, int slot, bool more_) {  // weights of K-step (tap, c) into ring slot `slot`
     const unsigned off = (unsigned)tap * tstride + ((unsigned)(c >> 1) * (unsigned)a.Cout_pad * BK + (unsigned)(c & 1) * H32_BK) * 2u;
-    if constexpr (false) {
-      dma16s(wbase + off, woff, wdst_u + slot * WSTAGE);  // every wave carries a piece and the step exists: nothing to select
-    } else {
-      const bool on = (decltype(ONC)::value || more_) && wreal;
-      dma16s(on ? wbase + off : zp64, on ? woff : 0u, on ? wdst_u + slot * WSTAGE : sink_u);
-    }
+    const bool on = more_ && wreal;
+    dma16s(on ? wbase + off : zp64, on ? woff : 0u, on ? wdst_u + slot * WSTAGE : sink_u);
   };
   auto issueX2 = [&](int c, int i, int buf, bool on) {   // halo piece i of chunk c into halo buffer `buf`
     const int c0 = c * H32_BK;
@@ -573,89 +563,61 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
     dma16v(ok ? base + off : zp64, on ? ldsX_u + buf * xbytes + i * 8192 : sink_u);
   };
 
-  float16v acc[M16 ? 1 : TM][M16 ? 1 : TN];
-  float4v acc16[M16 ? MI : 1][M16 ? NJ : 1];
-  if constexpr (M16) {
+  float4v acc16[MI][NJ];
 #pragma unroll
-    for (int i = 0; i < MI; ++i)
+  for (int i = 0; i < MI; ++i)
 #pragma unroll
-      for (int j = 0; j < NJ; ++j) acc16[i][j] = float4v{0.0f, 0.0f, 0.0f, 0.0f};
-    if constexpr (BMC >= 64) {
-      // the accumulators may start from a precomputed partial sum (convolution is linear in its input channels:
-      // the part of a GRU gate that only depends on the per-edge context features is computed once per edge)
-      if (a.accinit) {
+    for (int j = 0; j < NJ; ++j) acc16[i][j] = float4v{0.0f, 0.0f, 0.0f, 0.0f};
+  if constexpr (BMC >= 64) {
+    // the accumulators may start from a precomputed partial sum (convolution is linear in its input channels:
+    // the part of a GRU gate that only depends on the per-edge context features is computed once per edge)
+    if (a.accinit) {
 #pragma unroll
-        for (int j = 0; j < NJ; ++j) {
-          const int64_t m = pix_of(wn * 64 + j * 16 + (lane & 15));
-          if (FLAT && m < 0) continue;
+      for (int j = 0; j < NJ; ++j) {
+        const int64_t m = pix_of(wn * 64 + j * 16 + (lane & 15));
+        if (FLAT && m < 0) continue;
 #pragma unroll
-          for (int i = 0; i < MI; ++i) {
-            const int cg = cout0 + wm * (MI * 16) + i * 16 + 4 * (lane >> 4);
-            if constexpr (VAR == 1) {
-              const float4 v = *reinterpret_cast<const float4*>(reinterpret_cast<const float*>(a.accinit) + m * a.ai_ctot +
-                                                                a.ai_coff + cg);
-              acc16[i][j] = float4v{v.x, v.y, v.z, v.w};
-            } else {
-              const half4 v = *reinterpret_cast<const half4*>(a.accinit + m * a.ai_ctot + a.ai_coff + cg);
-              acc16[i][j] = float4v{(float)v[0], (float)v[1], (float)v[2], (float)v[3]};
-            }
+        for (int i = 0; i < MI; ++i) {
+          const int cg = cout0 + wm * (MI * 16) + i * 16 + 4 * (lane >> 4);
+          if constexpr (VAR == 1) {
+            const float4 v = *reinterpret_cast<const float4*>(reinterpret_cast<const float*>(a.accinit) + m * a.ai_ctot +
+                                                              a.ai_coff + cg);
+            acc16[i][j] = float4v{v.x, v.y, v.z, v.w};
+          } else {
+            const half4 v = *reinterpret_cast<const half4*>(a.accinit + m * a.ai_ctot + a.ai_coff + cg);
+            acc16[i][j] = float4v{(float)v[0], (float)v[1], (float)v[2], (float)v[3]};
           }
         }
       }
     }
-  } else {
-#pragma unroll
-    for (int i = 0; i < TM; ++i)
-#pragma unroll
-      for (int j = 0; j < TN; ++j)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.0f;
   }
 
   // fragment read addresses: weights are fixed per lane; the activation window of tap (dy, dx) starts at halo row
   // (wn + dy + 1) * 66 + pxh + dx + 1.
   const int l16 = lane & 15, lk = lane >> 4;
-  const int wa0 = M16 ? swz32<true>(wm * MI * 16 + l16, lk) : swz32<false>(wm * TM * 32 + lrow, lhalf);
+  const int wa0 = swz32(wm * MI * 16 + l16, lk);
   // Rl = this lane's halo row of the (-1, -1) window; the caller passes it through an empty asm once per chunk so
   // that the nine per-tap addresses are recomputed (5 VALU each) instead of being hoisted into 9+ VGPRs (spills)
-  const int Rl0 = (FLAT ? wn * HALO_TW : wn * HALO_PITCH) + pxh + (M16 ? l16 : lrow);
+  const int Rl0 = (FLAT ? wn * HALO_TW : wn * HALO_PITCH) + pxh + l16;
   auto mma_step = [&](const unsigned char* bw, const unsigned char* bx, int Rl, int dy, int dx) {
     const int rb = Rl + (dy + 1) * pitch + (dx + 1);
-    if constexpr (M16) {
-      const int xa0 = swz32<true>(rb, lk);
-      half8 wf[MI];
+    const int xa0 = swz32(rb, lk);
+    half8 wf[MI];
 #pragma unroll
-      for (int i = 0; i < MI; ++i) wf[i] = *reinterpret_cast<const half8*>(bw + (wa0 + i * 1024));
+    for (int i = 0; i < MI; ++i) wf[i] = *reinterpret_cast<const half8*>(bw + (wa0 + i * 1024));
 #pragma unroll
-      for (int j = 0; j < NJ; ++j) {
-        const half8 xf = *reinterpret_cast<const half8*>(bx + (xa0 + j * 1024));
+    for (int j = 0; j < NJ; ++j) {
+      const half8 xf = *reinterpret_cast<const half8*>(bx + (xa0 + j * 1024));
 #pragma unroll
-        for (int i = 0; i < MI; ++i)
-          acc16[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wf[i], xf, acc16[i][j], 0, 0, 0);
-      }
-    } else {
-      // kk = 1 flips chunk bit 1 (byte offset ^ 32)
-      const int xa0 = swz32<false>(rb, lhalf);
-#pragma unroll
-      for (int kk = 0; kk < 2; ++kk) {
-        half8 wf[TM], xf[TN];
-#pragma unroll
-        for (int i = 0; i < TM; ++i) wf[i] = *reinterpret_cast<const half8*>(bw + ((wa0 ^ (kk << 5)) + i * 2048));
-#pragma unroll
-        for (int j = 0; j < TN; ++j) xf[j] = *reinterpret_cast<const half8*>(bx + ((xa0 ^ (kk << 5)) + j * 2048));
-#pragma unroll
-        for (int i = 0; i < TM; ++i)
-#pragma unroll
-          for (int j = 0; j < TN; ++j)
-            acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(wf[i], xf[j], acc[i][j], 0, 0, 0);
-      }
+      for (int i = 0; i < MI; ++i)
+        acc16[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wf[i], xf, acc16[i][j], 0, 0, 0);
     }
   };
 
-  // the same step in two halves (16x16x32 form): all eight fragment reads of a tap, then its sixteen matrix instructions -
+  // the same step in two halves: all eight fragment reads of a tap, then its sixteen matrix instructions -
   // the 3x3 K loop puts the tap's LDS-DMA issue between them, in the shadow of the reads' latency
   auto load_frags = [&](const unsigned char* bw, const unsigned char* bx, int Rl, int dy, int dx, half8 (&wf)[MI], half8 (&xf)[NJ]) {
-    const int xa0 = swz32<true>(Rl + (dy + 1) * pitch + (dx + 1), lk);
+    const int xa0 = swz32(Rl + (dy + 1) * pitch + (dx + 1), lk);
 #pragma unroll
     for (int i = 0; i < MI; ++i) wf[i] = *reinterpret_cast<const half8*>(bw + (wa0 + i * 1024));
 #pragma unroll
@@ -691,19 +653,12 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
       auto tap_step = [&](auto TAPC) {
         constexpr int TAP = decltype(TAPC)::value;
         constexpr int T2 = TAP + 2;
-        if constexpr (M16) {
-          half8 wf[MI], xf[NJ];
-          load_frags(ldsW + (TAP % 3) * WSTAGE, bx, Rl, TAP / 3 - 1, TAP % 3 - 1, wf, xf);
-          if constexpr (T2 < 9) issueW2(T2, c, T2 % 3, std::true_type{}, true);
-          else issueW2(T2 - 9, c + 1, T2 % 3, std::false_type{}, more);
-          if constexpr (TAP < H32_XP) issueX2(c + 1, TAP, (c + 1) & 1, more && piece_used(TAP));
-          mma_frags(wf, xf);
-        } else {
-          if constexpr (T2 < 9) issueW2(T2, c, T2 % 3, std::true_type{}, true);
-          else issueW2(T2 - 9, c + 1, T2 % 3, std::false_type{}, more);
-          if constexpr (TAP < H32_XP) issueX2(c + 1, TAP, (c + 1) & 1, more && piece_used(TAP));
-          mma_step(ldsW + (TAP % 3) * WSTAGE, bx, Rl, TAP / 3 - 1, TAP % 3 - 1);
-        }
+        half8 wf[MI], xf[NJ];
+        load_frags(ldsW + (TAP % 3) * WSTAGE, bx, Rl, TAP / 3 - 1, TAP % 3 - 1, wf, xf);
+        if constexpr (T2 < 9) issueW2(T2, c, T2 % 3, true);
+        else issueW2(T2 - 9, c + 1, T2 % 3, more);
+        if constexpr (TAP < H32_XP) issueX2(c + 1, TAP, (c + 1) & 1, more && piece_used(TAP));
+        mma_frags(wf, xf);
         if constexpr (TAP == 0 || TAP == 4) asm volatile("s_waitcnt vmcnt(2)" ::: "memory");
         else if constexpr (TAP < 4) asm volatile("s_waitcnt vmcnt(3)" ::: "memory");
         else asm volatile("s_waitcnt vmcnt(1)" ::: "memory");
@@ -741,7 +696,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
   constexpr int NIT = BP * CPP / 512, PSTEP = 512 / CPP;
   const int ch = (tid % CPP) * 8, co = cout0 + ch, pl0 = tid / CPP;
   if constexpr (BMC >= 64) {
-    if constexpr (M16 && VAR == 2) {
+    if constexpr (VAR == 2) {
       {
         // raw fp32 accumulators (no bias, no activation) for a later launch to start from: lanes lk = 0..3 of a pixel
         // cover 16 consecutive channels = one 64-byte sector per store instruction and pixel
@@ -781,27 +736,13 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
         }
         return b;
       };
-      if constexpr (M16) {
 #pragma unroll
-        for (int i = 0; i < MI; ++i) {
-          const int cl = wm * (MI * 16) + i * 16 + 4 * lk;
-          const float4 b = bias4(cl);
+      for (int i = 0; i < MI; ++i) {
+        const int cl = wm * (MI * 16) + i * 16 + 4 * lk;
+        const float4 b = bias4(cl);
 #pragma unroll
-          for (int j = 0; j < NJ; ++j)
-            put(cl, wn * 64 + j * 16 + l16, b, acc16[i][j][0], acc16[i][j][1], acc16[i][j][2], acc16[i][j][3]);
-        }
-      } else {
-#pragma unroll
-        for (int i = 0; i < TM; ++i)
-#pragma unroll
-          for (int g = 0; g < 4; ++g) {
-            const int cl = wm * (TM * 32) + i * 32 + 8 * g + 4 * lhalf;
-            const float4 b = bias4(cl);
-#pragma unroll
-            for (int j = 0; j < TN; ++j)
-              put(cl, wn * 64 + j * 32 + lrow, b, acc[i][j][4 * g], acc[i][j][4 * g + 1], acc[i][j][4 * g + 2],
-                  acc[i][j][4 * g + 3]);
-          }
+        for (int j = 0; j < NJ; ++j)
+          put(cl, wn * 64 + j * 16 + l16, b, acc16[i][j][0], acc16[i][j][1], acc16[i][j][2], acc16[i][j][3]);
       }
     };
     const int actsel = a.epi == EPI_PLAIN ? a.act : (a.epi == EPI_Q ? VIPE_ACT_TANH : VIPE_ACT_SIGMOID);
@@ -880,21 +821,12 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
     // BMC = 32 (flow / confidence heads, eta, narrow plain convs): fp32 staging, activation after it
     constexpr int PITCH = BMC + 4;
     float* stage = reinterpret_cast<float*>(lds);
-    if constexpr (M16) {
 #pragma unroll
-      for (int i = 0; i < MI; ++i)
+    for (int i = 0; i < MI; ++i)
 #pragma unroll
-        for (int j = 0; j < NJ; ++j)
-          *reinterpret_cast<float4*>(stage + (wn * 64 + pxh + j * 16 + l16) * PITCH + i * 16 + 4 * lk) =
-              make_float4(acc16[i][j][0], acc16[i][j][1], acc16[i][j][2], acc16[i][j][3]);
-    } else {
-#pragma unroll
-      for (int g = 0; g < 4; ++g) {
-        const int pl = wn * 64 + pxh + lrow, cs = 8 * g + 4 * lhalf;
-        *reinterpret_cast<float4*>(stage + pl * PITCH + cs) =
-            make_float4(acc[0][0][4 * g], acc[0][0][4 * g + 1], acc[0][0][4 * g + 2], acc[0][0][4 * g + 3]);
-      }
-    }
+      for (int j = 0; j < NJ; ++j)
+        *reinterpret_cast<float4*>(stage + (wn * 64 + pxh + j * 16 + l16) * PITCH + i * 16 + 4 * lk) =
+            make_float4(acc16[i][j][0], acc16[i][j][1], acc16[i][j][2], acc16[i][j][3]);
     __syncthreads();
     float bv[8];
 #pragma unroll
@@ -967,7 +899,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
   const half_t* zp = reinterpret_cast<const half_t*>(g_zero_page);
 
   int xpix[H32_XP];
-  const int xk = (sl ^ swzf<true>(r16)) * 8;
+  const int xk = (sl ^ swzf(r16)) * 8;
 #pragma unroll
   for (int i = 0; i < H32_XP; ++i) {
     const int pce = wave + 8 * i;
@@ -996,7 +928,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
       }
     }
     // weights: tap `wave` (and tap 8 on wave 0): rows 0..15 of packed block tap * cs64 + c / 2, 64-byte half c & 1
-    const unsigned woff = (unsigned)(r16 * 64 + ((sl ^ swzf<true>(r16)) << 3)) * 2u;
+    const unsigned woff = (unsigned)(r16 * 64 + ((sl ^ swzf(r16)) << 3)) * 2u;
     const half_t* wb = a.w + ((int64_t)(wave * cs64 + (c >> 1)) * a.Cout_pad) * BK + (c & 1) * H32_BK;
     glds16_off(wb, woff, ldsW_a + buf * NRW_WBYTES + wave * 1024);
     if (wave == 0) {
@@ -1006,7 +938,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
   };
 
   float4v acc[2] = {float4v{0.f, 0.f, 0.f, 0.f}, float4v{0.f, 0.f, 0.f, 0.f}};
-  const int wa0 = swz32<true>(l16, lk);
+  const int wa0 = swz32(l16, lk);
   const int Rl0 = (FLAT ? wn * HALO_TW : wn * HALO_PITCH) + pxh + l16;
   issue(0, 0);
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -1018,7 +950,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
 #pragma unroll
     for (int tap = 0; tap < 9; ++tap) {
       const int rb = Rl0 + (tap / 3) * pitch + (tap % 3);
-      const int xa0 = swz32<true>(rb, lk);
+      const int xa0 = swz32(rb, lk);
       const half8 wf = *reinterpret_cast<const half8*>(bw + (wa0 + tap * 1024));
 #pragma unroll
       for (int j = 0; j < 2; ++j) {
@@ -1210,7 +1142,6 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
   for (int i = 0; i < 4; ++i)
 #pragma unroll
     for (int j = 0; j < 4; ++j) acc[i][j] = float4v{0.0f, 0.0f, 0.0f, 0.0f};
-  typedef _Float16 half4v __attribute__((ext_vector_type(4)));
 #pragma unroll
   for (int st = 0; st < 7; ++st) {
     half8 wf[4];
@@ -1223,8 +1154,8 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
     const int o0 = (wrow + (t0 / 7) * pitch + l16 + t0 % 7) * 8, o1 = (wrow + (t1 / 7) * pitch + l16 + t1 % 7) * 8;
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
-      const half4v lo = *reinterpret_cast<const half4v*>(ldsX + o0 + j * 128);
-      const half4v hi = *reinterpret_cast<const half4v*>(ldsX + o1 + j * 128);
+      const half4 lo = *reinterpret_cast<const half4*>(ldsX + o0 + j * 128);
+      const half4 hi = *reinterpret_cast<const half4*>(ldsX + o1 + j * 128);
       const half8 xf = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
 #pragma unroll
       for (int i = 0; i < 4; ++i) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wf[i], xf, acc[i][j], 0, 0, 0);
@@ -1333,7 +1264,7 @@ constexpr size_t MAX_LDS = 160 * 1024;
 
 // flat tiling of an H x W image with `pad` zero columns per row (see conv_halo32_kernel): fills a.f_*; false when a
 // halo buffer would not fit the kernel's four 1-KiB pieces per wave
-bool flat_geometry(ConvArgs& a, int pad, bool is1x1) {
+bool flat_geometry(ConvArgs& a, int pad) {
   a.f_wp = a.W + pad;
   a.f_hwp = a.H * a.f_wp;
   a.f_tiles = (a.f_hwp + 255) / 256;
@@ -1343,9 +1274,11 @@ bool flat_geometry(ConvArgs& a, int pad, bool is1x1) {
   a.f_xbytes = a.f_pieces * 1024;
   a.f_p1lo = (a.f_wp + 1) / 16;
   a.f_p1hi = (a.f_wp + 256) / 16;
-  (void)is1x1;
   return a.f_wp >= 2 && a.f_pieces <= 8 * H32_XP && a.f_hwp < (1 << 23);
 }
+
+// this call needs a tile kernel (initial accumulators, raw partial sums): the gather kernels are no fallback for it
+inline bool needs_tile_kernel(const ConvArgs& a) { return a.accinit || a.epi == EPI_PARTIAL || a.ai_f32; }
 
 template <int BMC, int KS, int VAR, bool FLAT>
 int launch_halo32(const ConvArgs& a, int tiles, int gy, size_t lds, hipStream_t s) {
@@ -1360,7 +1293,7 @@ int launch_halo_family(ConvArgs& a, int cp, int64_t M, hipStream_t s) {
   const bool split_ok = a.split >= a.Cin || a.split % H32_BK == 0;
   const int tiles = FLAT ? a.B * a.f_tiles : (int)(M / (HALO_TH * HALO_TW));
   const size_t xb = FLAT ? (size_t)a.f_xbytes : (size_t)H32_XBYTES;
-  if (a.accinit || a.epi == EPI_PARTIAL || a.ai_f32) {
+  if (needs_tile_kernel(a)) {
     // initial accumulators / raw partial sums: the 16x16x32 halo kernel with >= 64 output channels (fp32 initial
     // accumulators and partial sums: 3x3, >= 128 output channels)
     const bool ok = cp >= 64 && split_ok && !(a.KH == 3 && a.Cout <= 16) && !(a.epi == EPI_PARTIAL && a.Cout % 4 != 0) &&
@@ -1396,6 +1329,15 @@ int launch_halo_family(ConvArgs& a, int cp, int64_t M, hipStream_t s) {
   return launch_halo32<32, 1, 0, FLAT>(a, tiles, 1, lds, s);
 }
 
+// Dispatch, in this order:
+//  1. a call that needs a tile kernel on a grid no tile kernel takes: VIPE_EUNSUPPORTED;
+//  2. GLO, 128 -> 128 1x1 with `net` as its own input: conv1x1_glo_kernel (any grid);
+//  3. 1x1 / 3x3 with Cin != 4 on a grid of 4 x 64 tiles, or FLAT on any other grid up to 126 columns
+//     (launch_halo_family): the narrow kernel for 3x3 with at most 16 output channels, else conv_halo32_kernel by
+//     (BMC, KS, VAR); what the family does not take falls through, unless the call needs a tile kernel;
+//  4. 7x7 with Cin = 4, plain epilogue: conv7x7_c4_kernel, aligned or FLAT (falls through when the halo does not fit);
+//  5. the per-tap gather kernels, any shape: register staging for Cin = 4 (>= 128 output channels only) and for more
+//     than 32 taps, LDS-DMA otherwise.
 int launch_conv(ConvArgs& a, hipStream_t s) {
   int cp, cinp, kp;
   if (vipe_conv_packed_dims(a.Cout, a.Cin, a.KH, a.KW, &cp, &cinp, &kp) != VIPE_OK) return VIPE_EINVAL;
@@ -1413,8 +1355,8 @@ int launch_conv(ConvArgs& a, hipStream_t s) {
   const bool off32 = (int64_t)a.B * a.H * a.W < (1ll << 31);  // pixel indices are ints; byte offsets are formed in 64 bits
   const bool aligned = a.W % HALO_TW == 0 && a.H % HALO_TH == 0;
   const bool halo = sq13 && aligned && off32;
-  const bool flat = sq13 && !aligned && off32 && flat_geometry(a, a.KH == 3 ? 1 : 0, a.KH == 1);
-  if ((a.accinit || a.epi == EPI_PARTIAL || a.ai_f32) && !halo && !flat) return VIPE_EUNSUPPORTED;
+  const bool flat = sq13 && !aligned && off32 && flat_geometry(a, a.KH == 3 ? 1 : 0);
+  if (needs_tile_kernel(a) && !halo && !flat) return VIPE_EUNSUPPORTED;
   if (a.epi == EPI_GLO && a.KH == 1 && a.KW == 1 && a.Cin == 128 && a.Cout == 128 && cp == 128 && a.split >= a.Cin &&
       a.x0_ctot % 8 == 0 && a.x0_coff % 8 == 0 && a.net == a.x0 && a.net_ctot == a.x0_ctot && a.net_coff == a.x0_coff &&
       a.extra == nullptr) {
@@ -1425,10 +1367,10 @@ int launch_conv(ConvArgs& a, hipStream_t s) {
   }
   if (halo) {
     const int rc = launch_halo_family<false>(a, cp, M, s);
-    if (rc != VIPE_EUNSUPPORTED || a.accinit || a.epi == EPI_PARTIAL || a.ai_f32) return rc;
+    if (rc != VIPE_EUNSUPPORTED || needs_tile_kernel(a)) return rc;
   } else if (flat) {
     const int rc = launch_halo_family<true>(a, cp, M, s);
-    if (rc != VIPE_EUNSUPPORTED || a.accinit || a.epi == EPI_PARTIAL || a.ai_f32) return rc;
+    if (rc != VIPE_EUNSUPPORTED || needs_tile_kernel(a)) return rc;
   }
   if (small && a.KH == 7 && a.KW == 7 && cp % 128 == 0 && kp == 256 && a.epi == EPI_PLAIN && a.extra == nullptr &&
       (int64_t)a.B * a.H * a.W < (1ll << 31)) {
@@ -1439,7 +1381,7 @@ int launch_conv(ConvArgs& a, hipStream_t s) {
       conv7x7_c4_kernel<false><<<dim3((int)(M / (HALO_TH * HALO_TW)) * gy), 512, C7_LDS, s>>>(a, gy);
       return vipe_launch_status();
     }
-    flat_geometry(a, 3, false);
+    flat_geometry(a, 3);
     const size_t need = C7_WBYTES + (size_t)(256 + 6 * a.f_wp + 6) * 8;
     if (need <= MAX_LDS && a.f_hwp < (1 << 23) && a.f_wp >= 2) {
       static std::atomic<uint64_t> seen{0};
