@@ -26,6 +26,7 @@ extern "C" {
 #define VIPE_F16 0
 #define VIPE_F32 1
 #define VIPE_F64 2
+#define VIPE_U8 3 /* decoded 8-bit frames (vipe_frame_ingest only) */
 
 #define VIPE_OK 0
 #define VIPE_EINVAL (-1)   /* bad shape / null pointer / unsupported dtype */
@@ -602,6 +603,33 @@ int vipe_enc_conv(const void* d_x, const float* d_in_stats, const void* d_w, con
  * d_res == null: out = relu(IN(raw)).  All [B,HW,C] fp16. */
 int vipe_enc_finish(const void* d_raw, const float* d_raw_stats, const void* d_res, const float* d_res_stats,
                     void* d_out, int B, int HW, int C, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Native-resolution frame ingest: what SLAMSystem.run's StandardResizeStreamProcessor (vipe/slam/system.py:42-77),
+ * VideoFrame.resize / crop (vipe/streams/base.py:164-254), _precompute_features (system.py:183-205) and the sensor
+ * disparity lines of _add_keyframe (system.py:152-156) make of ONE view of one decoded frame, in one launch.
+ * ------------------------------------------------------------------------------------------- */
+/* [fused] The frame [H0,W0] is resampled to (h1,w1) - F.interpolate(mode="bilinear", size=(h1,w1)): align_corners=False,
+ * no antialiasing, scale = float(in) / float(out), src = max(fma(scale, dst + 0.5, -0.5), 0) (one fused operation, as
+ * torch's device kernel evaluates it), i1 = min(i0 + 1, in - 1), every other product and sum rounded on its own - and
+ * cropped to rows [top, top + H), columns [left, left + W).  H and W must be multiples of 8 and the crop must lie
+ * inside (h1,w1); anything else is VIPE_EINVAL.
+ *   d_rgb        [H0,W0,3], rgb_dtype VIPE_U8 (x / 255 before the resample), VIPE_F16 or VIPE_F32, values 0-1
+ *   d_mask       [H0,W0] bytes (torch.bool / uint8, non-zero = usable pixel) or NULL
+ *   d_depth      [H0,W0] f32 metric depth or NULL
+ *   d_images     [3,H,W] f32 planar: the resampled, cropped rgb (GraphBuffer.images)
+ *   d_x4         [H,W,4] f16: (images - mean) / std with a zero 4th lane - bit for bit what vipe_enc_prep makes of
+ *                d_images, so the encoders are fed without that pass
+ *   d_mask8      [H/8,W/8] bytes, 1 = INVALID: the resampled mask thresholded at > 0.9 (VideoFrame.resize), cropped,
+ *                resampled to 1/8 and thresholded at > 0.9 again, inverted (_precompute_features).  At exactly 1/8 the
+ *                second stage is the mean of the thresholded pixels at rows 8i+3, 8i+4 and columns 8j+3, 8j+4: a cell is
+ *                valid iff those four are, and only those four are computed.  Untouched when d_mask is NULL.
+ *   d_disps_sens [H/8,W/8] f32: the resampled, cropped depth at [3::8, 3::8], then d > 0 ? 1 / d : d.  Untouched when
+ *                d_depth is NULL.
+ * One output pixel per thread in 64 x 4 tiles; the 1/8 outputs come from the threads that own pixel (8i+3, 8j+3). */
+int vipe_frame_ingest(const void* d_rgb, int rgb_dtype, const unsigned char* d_mask, const float* d_depth, int H0, int W0,
+                      int h1, int w1, int top, int left, int H, int W, float* d_images, void* d_x4,
+                      unsigned char* d_mask8, float* d_disps_sens, void* stream);
 
 #ifdef __cplusplus
 }

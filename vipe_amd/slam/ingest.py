@@ -1,0 +1,114 @@
+"""Native-resolution frame ingest: the step the reference's `SLAMSystem.run` puts in front of the SLAM loop
+(vipe/slam/system.py:42-77, 215-218, 306-309) - every stream wrapped in a `StandardResizeStreamProcessor` that rescales
+each frame to an area of about 384 x 512 and centre-crops both sides to multiples of 8 (`VideoFrame.resize` / `crop`,
+vipe/streams/base.py:164-254), intrinsics rescaled on the way in and recovered to the original frame size on the way out.
+
+    StandardResize(h0, w0)     the size / crop policy and the intrinsics round trip (host arithmetic, float64)
+    ingest_frames(frames, ..)  one `vipe_frame_ingest` launch per view: the native frame is read once and everything
+                               `_precompute_features` / `_add_keyframe` need is written - images, the encoders'
+                               normalised fp16 input, the 1/8 invalid mask, the sensor disparities
+
+Decoding stays with the caller: frames arrive as tensors.  The nearest-neighbour `instance` channel of `VideoFrame` is
+not read by the SLAM path and is not carried."""
+import math
+
+import torch
+
+from .._lib import F16, F32, check, lib, ptr, require, stream_ptr
+
+U8 = 3  # VIPE_U8
+_RGB_CODE = {torch.uint8: U8, torch.float16: F16, torch.float32: F32}
+
+
+class StandardResize:
+    """`StandardResizeStreamProcessor` (system.py:42-77) for frames of `h0` x `w0` pixels.
+
+    size = (h1, w1), crop = (top, bottom, left, right), out_size = (H, W) after the crop; fac_x / fac_y / scx / scy as
+    the reference keeps them for `recover_intrinsics`."""
+
+    def __init__(self, h0, w0):
+        h0, w0 = int(h0), int(w0)
+        require(h0 > 0 and w0 > 0, "frame size must be positive")
+        scale = math.sqrt((384 * 512) / (h0 * w0))
+        h1, w1 = int(h0 * scale), int(w0 * scale)
+        crop_h, crop_w = h1 % 8, w1 % 8
+        top, left = crop_h // 2, crop_w // 2
+        self.native_size = (h0, w0)
+        self.size = (h1, w1)
+        self.crop = (top, crop_h - top, left, crop_w - left)
+        self.out_size = (h1 - crop_h, w1 - crop_w)
+        require(self.out_size[0] > 0 and self.out_size[1] > 0, "frame too elongated: nothing is left after the crop")
+        self.fac_x, self.fac_y = w0 / w1, h0 / h1
+        self.scx, self.scy = left, top
+
+    def forward_intrinsics(self, K):
+        """`VideoFrame.resize` then `crop` on [fx, fy, cx, cy, (MEI xi)] (base.py:193-197, 235-239)."""
+        (h0, w0), (h1, w1) = self.native_size, self.size
+        K = K.clone()
+        K[0:4:2] *= w1 / w0
+        K[1:4:2] *= h1 / h0
+        K[2] -= self.scx
+        K[3] -= self.scy
+        return K
+
+    def recover_intrinsics(self, K):
+        """system.py:71-77: intrinsics at SLAM resolution -> at the original frame size."""
+        K = K.clone()
+        K[2] += self.scx
+        K[3] += self.scy
+        K[0:4:2] *= self.fac_x
+        K[1:4:2] *= self.fac_y
+        return K
+
+
+def frame_ingest(rgb, resize, images, x4, mask=None, mask8=None, depth=None, disps_sens=None):
+    """One view through `vipe_frame_ingest`: rgb [H0,W0,3] uint8 / fp16 / fp32, mask [H0,W0] bool / uint8 or None,
+    depth [H0,W0] fp32 or None -> images [3,H,W] fp32, x4 [H,W,4] fp16, mask8 [H/8,W/8] bool (True = invalid),
+    disps_sens [H/8,W/8] fp32 (the last two only where their input is given), all preallocated by the caller."""
+    (H0, W0), (h1, w1), (H, W) = resize.native_size, resize.size, resize.out_size
+    require(rgb.is_cuda and rgb.is_contiguous() and tuple(rgb.shape) == (H0, W0, 3), f"rgb must be a contiguous device tensor [{H0},{W0},3]")
+    require(rgb.dtype in _RGB_CODE, "rgb must be uint8, float16 or float32")
+    require(tuple(images.shape) == (3, H, W) and images.dtype == torch.float32 and images.is_contiguous(), "images: [3,H,W] fp32")
+    require(tuple(x4.shape) == (H, W, 4) and x4.dtype == torch.float16 and x4.is_contiguous(), "x4: [H,W,4] fp16")
+    for t in (images, x4, mask, mask8, depth, disps_sens):
+        require(t is None or t.device == rgb.device, "all tensors must live on the frame's device")
+    if mask is not None:
+        require(mask.dtype in (torch.bool, torch.uint8) and mask.is_contiguous() and tuple(mask.shape) == (H0, W0), "mask: [H0,W0] bool / uint8")
+        require(mask8 is not None and mask8.dtype == torch.bool and mask8.is_contiguous()
+                and tuple(mask8.shape) == (H // 8, W // 8), "mask8: [H/8,W/8] bool")
+    if depth is not None:
+        require(depth.dtype == torch.float32 and depth.is_contiguous() and tuple(depth.shape) == (H0, W0), "depth: [H0,W0] fp32")
+        require(disps_sens is not None and disps_sens.dtype == torch.float32 and disps_sens.is_contiguous()
+                and tuple(disps_sens.shape) == (H // 8, W // 8), "disps_sens: [H/8,W/8] fp32")
+    top, _, left, _ = resize.crop
+    check(lib().vipe_frame_ingest(ptr(rgb), _RGB_CODE[rgb.dtype], ptr(mask), ptr(depth), H0, W0, h1, w1, top, left, H, W,
+                                  ptr(images), ptr(x4), ptr(mask8) if mask is not None else None,
+                                  ptr(disps_sens) if depth is not None else None, stream_ptr(rgb)), "vipe_frame_ingest")
+
+
+def ingest_frames(frames, resize, device):
+    """The per-view list of `Frame` of one time step -> (images [V,3,H,W] fp32, x4 [V,H,W,4] fp16, masks [V,h,w] bool
+    True = INVALID or None, disps_sens [V,h,w] fp32 or None) at `resize.out_size`, h = H/8, w = W/8.  `resize` is one
+    `StandardResize` or one per view (all of one size).  masks is None unless every view carries a mask
+    (`_precompute_features`); disps_sens is None unless a view carries metric depth, and rows of views without one
+    are left as allocated - the caller reads the rows of the views that have it."""
+    resizes = list(resize) if isinstance(resize, (list, tuple)) else [resize] * len(frames)
+    require(len(resizes) == len(frames), "one StandardResize per view")
+    H, W = resizes[0].out_size
+    V = len(frames)
+    images = torch.empty((V, 3, H, W), dtype=torch.float32, device=device)
+    x4 = torch.empty((V, H, W, 4), dtype=torch.float16, device=device)
+    with_mask = all(f.mask is not None for f in frames)
+    masks = torch.empty((V, H // 8, W // 8), dtype=torch.bool, device=device) if with_mask else None
+    with_depth = any(f.metric_depth is not None for f in frames)
+    disps = torch.empty((V, H // 8, W // 8), dtype=torch.float32, device=device) if with_depth else None
+    for v, (f, r) in enumerate(zip(frames, resizes)):
+        require(r.out_size == (H, W), "all views must share one size")
+        rgb = f.rgb.to(device)
+        if rgb.dtype not in _RGB_CODE:
+            rgb = rgb.float()
+        mask = f.mask.to(device).contiguous() if with_mask else None
+        depth = f.metric_depth.to(device=device, dtype=torch.float32).contiguous() if f.metric_depth is not None else None
+        frame_ingest(rgb.contiguous(), r, images[v], x4[v], mask, masks[v] if with_mask else None, depth,
+                     disps[v] if depth is not None else None)
+    return images, x4, masks, disps

@@ -76,12 +76,13 @@ class MotionFilter:
             self._coords0 = self.coords_grid(ht, wd, device=net.device)[None].repeat(V, 1, 1, 1).contiguous()
 
     @torch.no_grad()
-    def check(self, images, buffer_masks=None):
-        """images [V,3,H,W] fp32 RGB in [0,1] on the device; buffer_masks [V,h,w] bool (True = invalid) or None.
+    def check(self, images, buffer_masks=None, x4=None):
+        """images [V,3,H,W] fp32 RGB in [0,1] on the device; buffer_masks [V,h,w] bool (True = invalid) or None; x4
+        [V,H,W,4] fp16: the normalised images where the caller has them already (`ingest_frames`), else made here.
         Returns True when the frame is to become a keyframe (its features are then in f_fmap / f_net / f_inp)."""
         h, self._pending = getattr(self, "_pending", None), None
         if h is None or h["images"] is not images:  # nothing (or another frame) was prefetched: the whole check now
-            return self.finish(self.begin(images, buffer_masks))
+            return self.finish(self.begin(images, buffer_masks, x4=x4))
         kept = self.finish(h)
         side = h["stream"]
         if kept and side is not None:
@@ -93,7 +94,7 @@ class MotionFilter:
         return kept
 
     @torch.no_grad()
-    def prefetch(self, images, buffer_masks=None, stream=None):
+    def prefetch(self, images, buffer_masks=None, stream=None, x4=None):
         """Two-stage pipeline of a streaming system: ENQUEUE the first half of `check(images, buffer_masks)` now - on
         `stream`, a side stream that first joins the current one - and let the next `check` of these very tensors only
         collect the score.  The filter of frame f+1 depends on nothing but the last keyframe's features, which `check(f)`
@@ -105,10 +106,12 @@ class MotionFilter:
             images.record_stream(stream)
             if buffer_masks is not None:
                 buffer_masks.record_stream(stream)
-        self._pending = self.begin(images, buffer_masks, stream=stream)
+            if x4 is not None:
+                x4.record_stream(stream)
+        self._pending = self.begin(images, buffer_masks, stream=stream, x4=x4)
 
     @torch.no_grad()
-    def begin(self, images, buffer_masks=None, stream=None):
+    def begin(self, images, buffer_masks=None, stream=None, x4=None):
         """First half of `check`: feature encoder + one flow-update application against the last keyframe, the score on
         its way to pinned host memory - everything is ENQUEUED (on `stream`, default the current one), nothing is
         waited for.  A pipeline that filters frame t+1 on a side stream while the frontend optimises keyframe t on the
@@ -116,7 +119,8 @@ class MotionFilter:
         last keyframe's features, which `finish(t)` has already installed."""
         ctx = torch.cuda.stream(stream) if stream is not None else _null_ctx()
         with ctx:
-            x4 = normalize_images(images)
+            if x4 is None:
+                x4 = normalize_images(images)
             gmap = self.net.encode_features(images, x4)
             h = dict(images=images, x4=x4, gmap=gmap, masks=buffer_masks, stream=stream, score=None, event=None)
             if self.initialized:

@@ -1,6 +1,7 @@
 """`SLAMSystem` - host-side mirror of the reference's top-level driver (vipe/slam/system.py:51-316) over frames that are
-already decoded, resized and resident on the device (decoding / resizing / the monocular depth networks / sparse tracks /
-the rerun visualisation are outside the path):
+already decoded and resident on the device - resized by the caller, or at their native size with
+`run(..., native_resolution=True)` (`ingest.py`: the reference's resize / crop step as one fused kernel per view); decoding /
+the monocular depth networks / sparse tracks / the rerun visualisation are outside the path, SURVEY 8:
 
     pass 1  every frame through the motion filter; accepted frames (and the last one) become keyframes - features and
             context into the buffer, sensor disparities from the frame's metric depth or a caller-supplied depth model,
@@ -23,6 +24,7 @@ from ..ext.lietorch import SE3
 from .backend import BackendArgs, SLAMBackend
 from .buffer import GraphBuffer
 from .frontend import FrontendArgs, SLAMFrontend
+from .ingest import StandardResize, ingest_frames
 from .inner_filler import InfillArgs, InnerFiller
 from .interface import SLAMOutput
 from .motion_filter import DroidNet, MotionFilter
@@ -71,6 +73,7 @@ class SLAMSystem:
         self.droid_net = droid_net if droid_net is not None else DroidNet()
         self.metric_depth = depth_model  # system.py:114-127 builds it from `keyframe_depth`; here the caller's
         self.sparse_tracks = sparse_tracks
+        self._resizes = None  # one `StandardResize` per view inside `run(..., native_resolution=True)`, None outside it
         # system.py:91 builds a tracker from the config; here the caller's (`track_image(frames)` per frame of pass 1,
         # `enabled`, `compute_dense_disp_target_weight` for the BA's track term) or None = the reference's dummy
 
@@ -102,8 +105,18 @@ class SLAMSystem:
             masks = torch.stack(ms)
         return images, masks
 
-    def _add_keyframe(self, frame_idx, images, buffer_masks, frames, phase, reuse=None):
-        """system.py:131-165.  `reuse`: (fmap, net, inp) the motion filter has just computed for these very images."""
+    def _features(self, frames):
+        """-> (images, masks, x4, disps_sens) of one time step: `_precompute_features` (x4 and disps_sens None: the
+        frames are at SLAM resolution already), or with `native_resolution` the fused resize / crop of `ingest_frames`."""
+        if self._resizes is None:
+            return self._precompute_features(frames) + (None, None)
+        images, x4, masks, disps_sens = ingest_frames(frames, self._resizes, self.device)
+        return images, masks, x4, disps_sens
+
+    def _add_keyframe(self, frame_idx, images, buffer_masks, frames, phase, reuse=None, x4=None, disps_sens=None):
+        """system.py:131-165.  `reuse`: (fmap, net, inp) the motion filter has just computed for these very images.
+        `x4` / `disps_sens`: what `ingest_frames` made of these frames (native resolution) - the encoders' input and the
+        sensor disparities [V,h,w] of the views that carry metric depth."""
         b = self.buffer
         k = b.n_frames
         b.tstamp[k] = frame_idx
@@ -111,18 +124,22 @@ class SLAMSystem:
         if reuse is not None:
             b.fmaps[k], b.nets[k], b.inps[k] = reuse
         else:
-            b.fmaps[k] = self.droid_net.encode_features(images)
-            b.nets[k], b.inps[k] = self.droid_net.encode_context(images)
+            b.fmaps[k] = self.droid_net.encode_features(images, x4)
+            b.nets[k], b.inps[k] = self.droid_net.encode_context(images, x4)
         if buffer_masks is not None:
             b.masks[k] = buffer_masks
         for v, f in enumerate(frames):
             if k == 0:
                 assert f.intrinsics is not None, "the first frame must carry intrinsics"
-                b.intrinsics[v] = f.intrinsics.to(self.device)
+                K = f.intrinsics.to(self.device)
+                b.intrinsics[v] = K if self._resizes is None else self._resizes[v].forward_intrinsics(K)
             if f.metric_depth is not None:
-                d = f.metric_depth[3::8, 3::8].to(self.device)
                 assert not self.config.backend.optimize_intrinsics
-                b.disps_sens[k, v] = torch.where(d > 0, d.reciprocal(), d)
+                if disps_sens is not None:  # resized, cropped, subsampled and inverted by the ingest kernel
+                    b.disps_sens[k, v] = disps_sens[v]
+                else:
+                    d = f.metric_depth[3::8, 3::8].to(self.device)
+                    b.disps_sens[k, v] = torch.where(d > 0, d.reciprocal(), d)
             if f.pose is not None and phase == 1:
                 b.poses[k] = (SE3(b.rig[v]) * f.pose.inv()).data
                 b.touch()  # geometry of slot k rewritten from outside: prefetched frame distances are stale
@@ -150,20 +167,25 @@ class SLAMSystem:
         work0 = dict(_fg.WORK)
         self.timings, self.work = {}, {}
         t_start = time.perf_counter()
-        nxt = self._precompute_features(frames[0])
+        native = self._resizes is not None  # then x4 travels with the images: nobody runs vipe_enc_prep
+        # the filter gets the `x4` keyword in native mode only: a custom `motion_filter_cls` written against
+        # `check(images, masks)` / `prefetch(images, masks, stream=)` keeps working at SLAM resolution
+        ready = (lambda x4: {"x4": x4}) if native else (lambda x4: {})
+        nxt = self._features(frames[0])
         for frame_idx, fl in enumerate(frames):  # SLAM pass 1/2 (system.py:236-273)
-            images, masks = nxt
+            images, masks, x4, disps = nxt
             if self.sparse_tracks is not None:
                 self.sparse_tracks.track_image(fl)
-            kept = mf.check(images, masks)  # collects the prefetched first half when there is one
+            # collects the prefetched first half when there is one
+            kept = mf.check(images, masks, **ready(x4))
             is_keyframe = kept or frame_idx == total - 1
             if is_keyframe:  # a frame the filter kept has its features and context there already
                 self._add_keyframe(frame_idx, images, masks, fl, phase=1,
-                                   reuse=(mf.f_fmap, mf.f_net, mf.f_inp) if kept else None)
+                                   reuse=(mf.f_fmap, mf.f_net, mf.f_inp) if kept else None, x4=x4, disps_sens=disps)
             if frame_idx + 1 < total:
-                nxt = self._precompute_features(frames[frame_idx + 1])
+                nxt = self._features(frames[frame_idx + 1])
                 if side is not None:  # frame f+1's filter runs beside keyframe f's optimisation
-                    mf.prefetch(nxt[0], nxt[1], stream=side)
+                    mf.prefetch(nxt[0], nxt[1], stream=side, **ready(nxt[2]))
             self.frontend.run()
             # the backend in between corrects intrinsics / extrinsics early (system.py:269-272)
             if is_keyframe and b.n_frames in self.config.frontend_backend_iters:
@@ -205,26 +227,36 @@ class SLAMSystem:
         chunk = max(1, int(self.config.infill.infill_chunk_size))
         for c0 in range(0, total, chunk):
             idx = range(c0, min(c0 + chunk, total))
-            pre = [self._precompute_features(frames[i]) for i in idx]
+            pre = [self._features(frames[i]) for i in idx]
             feats = None
             if on_gpu and len(idx) > 1:
                 from .encoders import normalize_images
                 imgs = torch.cat([p[0] for p in pre], 0)
-                x4 = normalize_images(imgs)
+                x4 = torch.cat([p[2] for p in pre], 0) if native else normalize_images(imgs)
                 fmap = self.droid_net.encode_features(imgs, x4)
                 net, inp = self.droid_net.encode_context(imgs, x4)
                 V = pre[0][0].shape[0]
                 feats = [(fmap[j * V:(j + 1) * V], net[j * V:(j + 1) * V], inp[j * V:(j + 1) * V]) for j in range(len(idx))]
             for j, i in enumerate(idx):
-                self._add_keyframe(i, pre[j][0], pre[j][1], frames[i], phase=2, reuse=feats[j] if feats else None)
+                self._add_keyframe(i, pre[j][0], pre[j][1], frames[i], phase=2, reuse=feats[j] if feats else None,
+                                   x4=pre[j][2], disps_sens=pre[j][3])
                 if self.inner_filler.check() or i == total - 1:
                     self.inner_filler.compute()
         mark("pass2_done_seconds")
         self.work["total"] = {k: _fg.WORK[k] - work0[k] for k in work0}
 
     @torch.no_grad()
-    def run(self, frames, rig=None, camera_type="pinhole"):
-        """frames: sequence (length T) of per-view lists of `Frame` (a single `Frame` per step for one view)."""
+    def run(self, frames, rig=None, camera_type="pinhole", native_resolution=False):
+        """frames: sequence (length T) of per-view lists of `Frame` (a single `Frame` per step for one view).
+
+        native_resolution=False: the frames are at SLAM resolution already (sides multiples of 8) and the returned
+        intrinsics are at that resolution.  True: frames of any size, as decoded - every view goes through the
+        reference's `StandardResizeStreamProcessor` step (system.py:42-77, 215-218: bilinear resize to an area of about
+        384 x 512, centre crop to multiples of 8; `ingest_frames`, one fused kernel per view), `Frame.intrinsics` are
+        given at the native size and `SLAMOutput.intrinsics` come back recovered to it (system.py:306-309).  A
+        `sparse_tracks` tracker is handed the frames as they came (`track_image`), while the reference's sees the
+        resized, cropped ones: in native mode its `observations` must be in `StandardResize(...).out_size` pixel
+        coordinates (resize its input, or map its tracks with `forward_intrinsics`' scale and crop) - not converted here."""
         frames = [f if isinstance(f, (list, tuple)) else [f] for f in frames]
         total, n_views = len(frames), len(frames[0])
         assert total > 0 and all(len(f) == n_views for f in frames)
@@ -232,6 +264,12 @@ class SLAMSystem:
             assert n_views == 1, "Need rig for multiple views"
             rig = SE3.Identity(1)
         height, width = frames[0][0].rgb.shape[:2]
+        resizes = None
+        if native_resolution:
+            for f in frames[0]:  # system.py:222-223
+                assert tuple(f.rgb.shape[:2]) == (height, width), "all views must share one frame size"
+            resizes = [StandardResize(height, width) for _ in range(n_views)]
+            height, width = resizes[0].out_size
         self.config.frontend.has_init_pose = frames[0][0].pose is not None
         self._build_components(height, width, n_views, rig, camera_type)
         b = self.buffer
@@ -240,14 +278,18 @@ class SLAMSystem:
         if gc_was:
             gc.collect()
             gc.disable()
+        self._resizes = resizes  # read by `_features`, `_add_keyframe` and `_run_passes`, for the two passes only
         try:
             self._run_passes(frames, total)
         finally:
+            self._resizes = None
             if gc_was:
                 gc.enable()
         filled = self.inner_filler.get_result()
         if filled.poses.data.shape[0] != total:
             raise ValueError("fewer poses than frames: the frame sequence changed between the passes")
         slam_map = b.extract_slam_map(filter_thresh=self.config.map_filter_thresh)
-        return SLAMOutput(trajectory=filled.poses.inv(), intrinsics=b.intrinsics.clone(), rig=SE3(b.rig.clone()),
-                          slam_map=slam_map)
+        intrinsics = b.intrinsics.clone()
+        if resizes is not None:
+            intrinsics = torch.stack([r.recover_intrinsics(intrinsics[v]) for v, r in enumerate(resizes)])
+        return SLAMOutput(trajectory=filled.poses.inv(), intrinsics=intrinsics, rig=SE3(b.rig.clone()), slam_map=slam_map)
