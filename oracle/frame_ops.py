@@ -28,18 +28,20 @@ def rel_se3(pi, pj):
     return tj - _act_so3(q, ti), q
 
 
-def _grid(ht, wd):
-    v, u = np.meshgrid(np.arange(ht, dtype=np.float32), np.arange(wd, dtype=np.float32), indexing="ij")
+def _grid(ht, wd, dtype=np.float32):
+    v, u = np.meshgrid(np.arange(ht, dtype=dtype), np.arange(wd, dtype=dtype), indexing="ij")
     return u, v
 
 
-def frame_distance(poses, disps, intrinsics, pi, pj, qi, qj, di, beta):
-    """geom_kernels.cu:521-676."""
-    poses, disps, intrinsics = (np.asarray(a, np.float32) for a in (poses, disps, intrinsics))
-    beta = np.float32(beta)
+def frame_distance(poses, disps, intrinsics, pi, pj, qi, qj, di, beta, dtype=np.float32, with_share=False):
+    """geom_kernels.cu:521-676.  `dtype` is the precision of the arithmetic (the kernel's float32, or float64 on the same
+    float32 inputs); `with_share` also returns each pair's valid share, the number the 0.75 test looks at."""
+    poses, disps, intrinsics = (np.asarray(a, np.float32).astype(dtype, copy=False) for a in (poses, disps, intrinsics))
+    beta = np.dtype(dtype).type(np.float32(beta))
     _, ht, wd = disps.shape
-    u, v = _grid(ht, wd)
-    out = np.zeros(len(pi), np.float32)
+    u, v = _grid(ht, wd, dtype)
+    out = np.zeros(len(pi), dtype)
+    share = np.zeros(len(pi), np.float64)
     for b in range(len(pi)):
         t, q = rel_se3(poses[pi[b]], poses[pj[b]])
         fxi, fyi, cxi, cyi = intrinsics[qi[b]]
@@ -57,17 +59,21 @@ def frame_distance(poses, disps, intrinsics, pi, pj, qi, qj, di, beta):
         accum += (1 - beta) * np.sum(dist[ok], dtype=np.float64)
         valid += (1 - beta) * ok.sum()
         total = float(ht * wd)
+        share[b] = valid / (total + 1e-8)
         out[b] = 1000.0 if valid / (total + 1e-8) < 0.75 else accum / valid
-    return out
+    return (out, share) if with_share else out
 
 
-def depth_filter(poses, disps, intrinsics, inds, thresh):
-    """geom_kernels.cu:678-793 -> counter [num,ht,wd] (integer valued float32)."""
-    poses, disps, intr = (np.asarray(a, np.float32) for a in (poses, disps, intrinsics))
+def depth_filter(poses, disps, intrinsics, inds, thresh, dtype=np.float32, with_margin=False):
+    """geom_kernels.cu:678-793 -> counter [num,ht,wd] (integer valued float32).  `with_margin` also returns, per pixel,
+    the smallest | |1/dj - 1/d| - thresh | over the taps of its in-bounds neighbours (inf where there are none): how far
+    the pixel's count is from changing."""
+    poses, disps, intr = (np.asarray(a, np.float32).astype(dtype, copy=False) for a in (poses, disps, intrinsics))
     n, ht, wd = disps.shape
     fx, fy, cx, cy = intr
-    u, v = _grid(ht, wd)
+    u, v = _grid(ht, wd, dtype)
     out = np.zeros((len(inds), ht, wd), np.float32)
+    margin = np.full((len(inds), ht, wd), np.inf)
     for b, ix in enumerate(inds):
         for nb in range(6):
             jx = ix - nb - 1 if nb < 3 else ix + nb - 2
@@ -88,17 +94,21 @@ def depth_filter(poses, disps, intrinsics, inds, thresh):
                 inv = 1.0 / dj.astype(np.float64)
                 for (a, c) in ((0, 0), (0, 1), (1, 0), (1, 1)):
                     dn = disps[jx][v0c + a, u0c + c].astype(np.float64)
-                    hit |= np.abs(inv - 1.0 / dn) < float(np.float32(thresh[b]))
+                    gap = np.abs(inv - 1.0 / dn)
+                    hit |= gap < float(np.float32(thresh[b]))
+                    margin[b] = np.where(ok, np.fmin(margin[b], np.abs(gap - float(np.float32(thresh[b])))), margin[b])
             out[b] += (ok & hit).astype(np.float32)
-    return out
+    return (out, margin) if with_margin else out
 
 
-def projmap(poses, disps, intrinsics, ii, jj):
-    poses, disps, intr = (np.asarray(a, np.float32) for a in (poses, disps, intrinsics))
+def projmap(poses, disps, intrinsics, ii, jj, dtype=np.float32, with_depth=False):
+    """geom_kernels.cu:434-519.  `with_depth` also returns the target-frame depth Xj.z [E,ht,wd] both branches look at."""
+    poses, disps, intr = (np.asarray(a, np.float32).astype(dtype, copy=False) for a in (poses, disps, intrinsics))
     _, ht, wd = disps.shape
     fx, fy, cx, cy = intr
-    u, v = _grid(ht, wd)
-    coords = np.zeros((len(ii), ht, wd, 3), np.float32)
+    u, v = _grid(ht, wd, dtype)
+    coords = np.zeros((len(ii), ht, wd, 3), dtype)
+    depth = np.zeros((len(ii), ht, wd), dtype)
     valid = np.zeros((len(ii), ht, wd, 1), np.float32)
     for b in range(len(ii)):
         t, q = rel_se3(poses[ii[b]], poses[jj[b]])
@@ -109,15 +119,16 @@ def projmap(poses, disps, intrinsics, ii, jj):
             coords[b, ..., 0] = np.where(ok, fx * (Xj[..., 0] / Xj[..., 2]) + cx, u)
             coords[b, ..., 1] = np.where(ok, fy * (Xj[..., 1] / Xj[..., 2]) + cy, v)
         valid[b, ..., 0] = Xj[..., 2] > MIN_DEPTH
-    return coords, valid
+        depth[b] = Xj[..., 2]
+    return (coords, valid, depth) if with_depth else (coords, valid)
 
 
-def iproj(poses, disps, intrinsics):
-    poses, disps, intr = (np.asarray(a, np.float32) for a in (poses, disps, intrinsics))
+def iproj(poses, disps, intrinsics, dtype=np.float32):
+    poses, disps, intr = (np.asarray(a, np.float32).astype(dtype, copy=False) for a in (poses, disps, intrinsics))
     n, ht, wd = disps.shape
     fx, fy, cx, cy = intr
-    u, v = _grid(ht, wd)
-    out = np.zeros((n, ht, wd, 3), np.float32)
+    u, v = _grid(ht, wd, dtype)
+    out = np.zeros((n, ht, wd, 3), dtype)
     for b in range(n):
         Xi = np.stack([(u - cx) / fx, (v - cy) / fy, np.ones_like(u)], -1)
         X = _act_so3(poses[b, 3:], Xi) + disps[b][..., None] * poses[b, :3]
