@@ -38,6 +38,12 @@ def test_argument_errors_do_not_launch():
     assert 20e6 < nbytes < 200e6  # E_j rows dominate: 276 * 6 * 3072 * 4 B
 
 
+def test_scatter_mean_rows_stub_is_unsupported():
+    """`vipe_scatter_mean_rows_f16` is declared but superseded by `vipe_segment_mean_nhwc_f16`: it ignores its arguments
+    and says so instead of pretending to have run (nothing is launched, so this needs no GPU)"""
+    assert _lib.lib().vipe_scatter_mean_rows_f16(None, None, None, 0, 0, 0, None) == -3  # VIPE_EUNSUPPORTED
+
+
 def test_lietorch_host_path_matches_oracle():
     """lietorch_ext on CPU tensors runs the library's host loop over the same closed forms as the kernels."""
     from vipe_amd.ext.lietorch import SE3, SO3
