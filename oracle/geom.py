@@ -201,3 +201,20 @@ def reproject(poses, disps, intr, rig, pi, pj, qi, qj, di, model="pinhole", jaco
         out["Jfi"] = np.stack(cols, axis=-1).astype(dt)
         out["Jfj"] = Jfj.astype(dt)
     return out
+
+
+def motion_features(coords, target, ht, wd):
+    """factor_graph.py:259-261: clamp(cat(coords - grid, target - coords), -64, 64), channels first.
+
+    coords, target [M,ht,wd,2] float32.  Float32 arithmetic on the GIVEN coordinates (one subtraction per channel, then
+    the clamp), so it is exact to the bit for a kernel that does the same to the same coordinates.
+    Returns (fp32 [M,4,ht,wd], fp16 [M,4,ht,wd]); the fp16 one is the round-to-nearest-even cast of the fp32 one.
+    """
+    coords = np.asarray(coords, dtype=np.float32)
+    target = np.asarray(target, dtype=np.float32)
+    u, v = pixel_grid(ht, wd, np.float32)
+    grid = np.stack([u, v], axis=-1)
+    m = np.concatenate([coords - grid, target - coords], axis=-1)
+    m = np.clip(m, np.float32(-64.0), np.float32(64.0)).astype(np.float32)
+    m = np.ascontiguousarray(np.moveaxis(m, -1, 1))
+    return m, m.astype(np.float16)

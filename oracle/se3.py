@@ -245,3 +245,49 @@ def se3_identity(n, dtype=np.float32):
     X = np.zeros((n, 7), dtype=dtype)
     X[:, 6] = 1
     return X
+
+
+# ----------------------------------------------------------------------------- SO3 ops with a point / tangent operand
+
+
+def so3_adj(q, a):
+    """so3.h:57-59, 82: Adj(X) a = R a."""
+    return np.einsum("...ij,...j->...i", so3_matrix(q), a)
+
+
+def so3_adjT(q, a):
+    """so3.h:84: Adj(X)^T a = R^T a."""
+    return np.einsum("...ji,...j->...i", so3_matrix(q), a)
+
+
+def so3_act4(q, p):
+    """so3.h:52-55 on homogeneous points: [R p_xyz, p_w]."""
+    return np.concatenate([so3_act(q, p[..., :3]), p[..., 3:4]], axis=-1)
+
+
+def so3_matrix4(q):
+    """so3.h:63-68: blockdiag(R, 1)."""
+    q = np.asarray(q)
+    T = np.zeros(q.shape[:-1] + (4, 4), dtype=q.dtype)
+    T[..., :3, :3] = so3_matrix(q)
+    T[..., 3, 3] = 1
+    return T
+
+
+def so3_projector(q):
+    """so3.h:72-80: d(embedding)/d(tangent) = 1/2 [[w I - q^], [-q^T]], padded to 4 x 4 (last column zero)."""
+    q = quat_normalize(np.asarray(q))
+    P = np.zeros(q.shape[:-1] + (4, 4), dtype=q.dtype)
+    P[..., :3, :3] = 0.5 * (q[..., 3, None, None] * np.eye(3, dtype=q.dtype) + hat(-q[..., :3]))
+    P[..., 3, :3] = -0.5 * q[..., :3]
+    return P
+
+
+def se3_projector(X):
+    """se3.h:107-115: [[I, -t^, 0], [0, P_so3]] as 7 x 7 (last column zero)."""
+    t, q = se3_split(X)
+    P = np.zeros(X.shape[:-1] + (7, 7), dtype=X.dtype)
+    P[..., :3, :3] = np.eye(3, dtype=X.dtype)
+    P[..., :3, 3:6] = hat(-t)
+    P[..., 3:, 3:] = so3_projector(q)
+    return P
