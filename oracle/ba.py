@@ -30,13 +30,20 @@ def bundle_adjustment(
     poses, disps, disps_sens, intrinsics, rig, target, weight, disp_damping, ii, jj, t0, t1, n_iters,
     pose_damping, pose_ep, motion_only=False, limited_disp=False, optimize_intrinsics=False,
     optimize_rig_rotation=False, model="pinhole", alpha=0.001, dtype=np.float64, solver="dense",
-    cross_view_idx=None, return_debug=False, weight_scale=0.001, intrinsics_factor=8.0,
+    cross_view_idx=None, return_debug=False, weight_scale=0.001, intrinsics_factor=8.0, mutate=(),
 ):
     """buffer.py:373-525.
 
     poses [Nbuf,7]; disps, disps_sens, disp_damping [Nbuf,V,ht,wd]; intrinsics [V,4+D] full-res;
     rig [V,7]; target, weight [E*V,P,2]; ii, jj [E].  Returns updated copies
-    (poses, disps, intrinsics, rig) and optionally a list of per-iteration debug dicts.
+    (poses, disps, intrinsics, rig) and optionally a list of per-iteration debug dicts: next to the blocks of the
+    normal equations, the target-side depth "Z" and the validity mask "valid" [M,P] of every term, "dz" = the disparity
+    step BEFORE the rejection of retractor.py:41, and the free / fixed sets "free_pose", "fixed_pose", "free_disp",
+    "fixed_disp" (pose ids and disparity-frame ids).
+
+    `mutate` names deliberate errors, for the tests that prove a case can tell them apart (tests/test_oracle_ba_cases.py);
+    empty, nothing changes: "no_valid" drops the validity mask, "abs_reject" rejects |dz| > 10 instead of dz > 10,
+    "no_clamp" leaves out the final clamp, "fix_target_only" also fixes poses outside [t0, t1) that are only targets.
     """
     dt = np.dtype(dtype)
     poses = np.array(poses, dtype=dt)
@@ -58,7 +65,9 @@ def bundle_adjustment(
     D = intrinsics.shape[1] - 4
 
     # ---- fixed sets (buffer.py:462-465, 490-493; terms.py:69-72)
-    pi_unique = np.unique(ii)
+    mutate = frozenset(mutate)
+    assert mutate <= {"no_valid", "abs_reject", "no_clamp", "fix_target_only"}, mutate
+    pi_unique = np.unique(np.concatenate([ii, jj])) if "fix_target_only" in mutate else np.unique(ii)
     if t0 < t1:
         fixed_pose = set(pi_unique[(pi_unique < t0) | (pi_unique >= t1)].tolist())
         all_pose_fixed = False
@@ -94,6 +103,8 @@ def bundle_adjustment(
                            jacobian=True, jacobian_f=optimize_intrinsics)
         r = (g["coords"].reshape(M, P, 2) - target)  # terms.py:242
         w = g["valid"].reshape(M, P, 1) * wgt  # terms.py:195
+        if "no_valid" in mutate:
+            w = wgt.copy()
         Ji = g["Ji"].reshape(M, P, 2, 6)
         Jj = g["Jj"].reshape(M, P, 2, 6)
         Jz = g["Jz"].reshape(M, P, 2)
@@ -204,12 +215,18 @@ def bundle_adjustment(
                     intrinsics[idx, 4:] += step[1:] * dt.type(0.01)
         for k in free_disp:
             step = np.where(dz[k] > 10, np.zeros_like(dz[k]), dz[k])  # retractor.py:41
+            if "abs_reject" in mutate:
+                step = np.where(np.abs(dz[k]) > 10, np.zeros_like(dz[k]), dz[k])
             dflat[k] += step
         if return_debug:
             debug.append({"H": H, "v": v, "S": S, "g": gv, "dx": dx, "dz": dz, "C": C, "w": wv,
-                          "blocks": blocks, "off": off, "r": r, "wgt": w})
+                          "blocks": blocks, "off": off, "r": r, "wgt": w,
+                          "Z": g["Z"].reshape(M, P), "valid": g["valid"].reshape(M, P) > 0,
+                          "free_pose": list(pose_ids), "fixed_pose": sorted(set(pi.tolist() + pj.tolist()) - set(pose_ids)),
+                          "free_disp": list(free_disp), "fixed_disp": sorted(fixed_disp)})
 
-    np.maximum(dflat, dt.type(1e-3), out=dflat)  # buffer.py:525 (whole buffer)
+    if "no_clamp" not in mutate:
+        np.maximum(dflat, dt.type(1e-3), out=dflat)  # buffer.py:525 (whole buffer)
     out = (poses, dflat.reshape(Nbuf, V, ht, wd), intrinsics, rig)
     return out + (debug,) if return_debug else out
 

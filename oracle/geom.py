@@ -155,7 +155,7 @@ def pinhole_of(intr, model):
 def reproject(poses, disps, intr, rig, pi, pj, qi, qj, di, model="pinhole", jacobian=False, jacobian_f=False):
     """geom.py:187-298. poses [N,7], disps [NV,ht,wd], intr [Q,4+D] already at 1/8 scale, rig [Q,7].
 
-    Returns coords [M,ht,wd,2], valid [M,ht,wd], and if jacobian:
+    Returns coords [M,ht,wd,2], valid [M,ht,wd], Z [M,ht,wd] (target-side depth before the clamp), and if jacobian:
     Ji, Jj [M,ht,wd,2,6], Jz [M,ht,wd,2]; if jacobian_f: Jfi, Jfj [M,ht,wd,2,1+D].
     """
     dt = disps.dtype
@@ -172,7 +172,7 @@ def reproject(poses, disps, intr, rig, pi, pj, qi, qj, di, model="pinhole", jaco
 
     coords, Jp, Jfj = proj_points(X1, intr[qj], model, jac=jacobian, compute_jf=jacobian_f)
     valid = ((X1[..., 2] > dt.type(MIN_DEPTH)) & (X0[..., 2] > dt.type(MIN_DEPTH))).astype(dt)  # geom.py:263
-    out = {"coords": coords, "valid": valid}
+    out = {"coords": coords, "valid": valid, "Z": X1[..., 2]}
     if not jacobian:
         return out
 

@@ -330,6 +330,26 @@ def gen_ba_rig(R):
     np.savez_compressed(path, **out)
 
 
+def gen_ba_edges(R):
+    """The cases of oracle/ba_cases.py (validity, zero support, step rejection, ragged and large plans) through the
+    reference Solver: mono through `reference_ba`, the 8-view rig through `reference_ba_rig`.  OUTPUTS only - the inputs
+    are re-created from the seeds by the tests."""
+    from oracle import ba_cases as bc
+    out = {}
+    for name in bc.ALL:
+        c = bc.case(name)
+        g = c.g
+        if c.rig:
+            p, d, k, r, en = reference_ba_rig(R, g, **c.bk)
+        else:
+            p, d, k, en = reference_ba(R, g.poses, g.disps, g.disps_sens, c.intr, g.target, g.weight, g.eta, g.ii, g.jj,
+                                       camera=c.cam, **c.bk)
+            r = ose3.se3_identity(1).astype(np.float32)
+        out[name + "/poses"], out[name + "/disps"], out[name + "/intrinsics"], out[name + "/rig"] = p, d, k, r
+        print(name, "energy", en)
+    np.savez_compressed(os.path.join(HERE, "ba_edges_reference.npz"), **out)
+
+
 def gen_reproject(R):
     """geom.iproj_i_proj_j_disp values + Jacobians, pinhole and MEI (geom.py:187-298)."""
     out = {}
@@ -675,6 +695,9 @@ if __name__ == "__main__":
     if os.environ.get("GOLDEN_ONLY") == "ba_tracks":
         gen_ba_tracks(R)
         sys.exit(0)
+    if os.environ.get("GOLDEN_ONLY") == "ba_edges":
+        gen_ba_edges(R)
+        sys.exit(0)
     if os.environ.get("GOLDEN_ONLY") == "encoder":
         gen_encoder(R)
         sys.exit(0)
@@ -684,6 +707,7 @@ if __name__ == "__main__":
     gen_ba(R)
     gen_ba_rig(R)
     gen_ba_tracks(R)
+    gen_ba_edges(R)
     gen_splat(R)
     gen_update_module(R)
     gen_corr(R)

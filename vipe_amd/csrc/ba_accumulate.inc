@@ -498,7 +498,9 @@ __global__ __launch_bounds__(TILE) __attribute__((amdgpu_waves_per_eu(3, 3))) vo
         atomicAdd(&w.S[(int64_t)nrow * w.ld + gc], -(double)val);
       } else {
         const int gr = gmap(row);
-        if (gr >= 0) s_add(w, gr, gc, -(double)val);
+        // two terms with the same target (a duplicated edge) put two local rows on one unknown: their cross product
+        // belongs to the diagonal entry twice, (r1, r2) and (r2, r1), and the local lower triangle holds it once
+        if (gr >= 0) s_add(w, gr, gc, (gr == gc && row != cc) ? -2.0 * (double)val : -(double)val);
       }
     }
   }
@@ -926,7 +928,7 @@ __global__ __launch_bounds__(TILE) void ba_schur_kernel(BAArgs a) {
       const int gr = rowg[ra], gc = rowg[16 + cb];
       if (row < NR && cc <= row && cc != NR - 1 && gc >= 0) {
         if (row == NR - 1) atomicAdd(&w.S[(int64_t)nrow * w.ld + gc], -(double)val);
-        else if (gr >= 0) s_add(w, gr, gc, -(double)val);
+        else if (gr >= 0) s_add(w, gr, gc, (gr == gc && row != cc) ? -2.0 * (double)val : -(double)val);  // duplicated edge: see ba_accum_mfma_kernel
       }
     }
   }

@@ -61,5 +61,5 @@ __global__ __launch_bounds__(TILE) void ba_retract_kernel(BAArgs a) {
 
 __global__ void clamp_min_kernel(float* __restrict__ x, int64_t n, float lo) {
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
-    x[i] = fmaxf(x[i], lo);  // NaN stays NaN? fmaxf(NaN, lo) = lo; torch.clamp keeps NaN - disparities are finite here
+    x[i] = fmaxf(x[i], lo);  // fmaxf(NaN, lo) = lo where torch.clamp keeps the NaN: on purpose, a NaN disparity leaves as lo (DESIGN.md section 2)
 }
