@@ -631,6 +631,23 @@ int vipe_frame_ingest(const void* d_rgb, int rgb_dtype, const unsigned char* d_m
                       int h1, int w1, int top, int left, int H, int W, float* d_images, void* d_x4,
                       unsigned char* d_mask8, float* d_disps_sens, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Full-resolution keyframe disparity: DROID-SLAM's learned convex upsampling (cvx_upsample), the consumer of the
+ * update operator's GraphAgg.upmask head.  An addition: the reference computes the mask and discards it
+ * (factor_graph.py:269).
+ * ------------------------------------------------------------------------------------------- */
+/* out[r, 8y+dy, 8x+dx, c] = sum_k softmax_k(mask[s, y, x, k*64 + dy*8 + dx]) * data[r, y+ky-1, x+kx-1, c] with tap
+ * k = ky*3 + kx (ky, kx in 0..2), sub-pixel (dy, dx) in 0..7, data read as zero outside the grid, r = d_rows[s] or, with
+ * d_rows NULL, r = s.  The softmax runs in f32 with the maximum subtracted.
+ *   d_mask  [N,h,w,576] channels-last, mask_dtype VIPE_F16 (what the operator writes) or VIPE_F32
+ *   d_data  [R,h,w,C] f32, C in 1..4 (C > 4: VIPE_EUNSUPPORTED)
+ *   d_out   [R,8h,8w,C] f32; rows that d_rows does not name are not written
+ *   d_rows  [N] int64 or NULL (then N <= R); mask rows whose index lies outside [0, R) are skipped
+ * d_mask and d_out must be 16-byte aligned.  N == 0: VIPE_OK, no launch.  One launch, flat over the N*h*w coarse
+ * pixels: 16 per workgroup, a thread owns 4 x-adjacent sub-pixels (8- / 16-byte mask loads, 16-byte stores). */
+int vipe_convex_upsample(const void* d_mask, int mask_dtype, const float* d_data, float* d_out, const int64_t* d_rows,
+                         int N, int R, int h, int w, int C, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

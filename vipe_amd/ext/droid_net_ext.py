@@ -310,3 +310,41 @@ def corr_lookup_conv1x1(levels, coords, w_packed, bias, out, out_coff=0, cout=12
                                          ptr(slots) if slots is not None else None, layout, stream_ptr(coords)),
           "corr_lookup_conv1x1")
     return out
+
+
+def cvx_upsample(data, mask, rows=None, out=None, mask_layout="nhwc"):
+    """Learned convex upsampling (DROID-SLAM's `cvx_upsample`; an addition - the reference discards the mask it would
+    consume, factor_graph.py:269): out[r, 8y+dy, 8x+dx, c] = sum_k softmax_k(mask[s, y, x, k*64 + dy*8 + dx]) *
+    data[r, y+ky-1, x+kx-1, c], k = ky*3 + kx, zero outside the grid, r = rows[s] (rows None: r = s).
+
+    data [R,h,w,C] f32 with C in 1..4; mask [N,h,w,576] f16 / f32 channels-last, what `UpdateEngine.forward_nhwc(...,
+    want_upmask=True)` returns - or, with mask_layout="nchw", the reference-shaped [N,576,h,w] (also [1,N,576,h,w]) of
+    `UpdateEngine.forward`, permuted here (tests and callers; the hot path never permutes); rows int64 [N] or None;
+    out [R,8h,8w,C] f32 (fresh and zero-filled when None).  Rows of `out` that `rows` does not name are left as they are.
+    The single route from Python to `vipe_convex_upsample`: the factor graph calls this function and nothing else."""
+    if not (data.is_cuda and mask.is_cuda):
+        raise NotImplementedError("cvx_upsample: device tensors only (vipe_convex_upsample is a HIP kernel)")
+    require(mask_layout in ("nhwc", "nchw"), "mask_layout must be 'nhwc' or 'nchw'")
+    if mask_layout == "nchw":
+        if mask.dim() == 5:
+            mask = mask.reshape(-1, *mask.shape[2:])
+        require(mask.dim() == 4 and mask.shape[1] == 576, "nchw mask must be [N,576,h,w]")
+        mask = mask.permute(0, 2, 3, 1).contiguous()
+    require(data.dim() == 4 and data.dtype == torch.float32, "data must be [R,h,w,C] float32")
+    require(mask.dim() == 4 and mask.shape[3] == 576 and mask.dtype in (torch.float16, torch.float32),
+            "mask must be [N,h,w,576] half/float")
+    R, h, w, C = data.shape
+    N = int(mask.shape[0])
+    require(tuple(mask.shape[1:3]) == (h, w), "mask and data grids differ")
+    if out is None:
+        out = torch.zeros((R, 8 * h, 8 * w, C), dtype=torch.float32, device=data.device)
+    require(tuple(out.shape) == (R, 8 * h, 8 * w, C) and out.dtype == torch.float32, "out must be [R,8h,8w,C] float32")
+    check_gpu_contig(data, mask, out)
+    if rows is not None:
+        check_gpu_contig(rows)
+        require(rows.dtype == torch.int64 and tuple(rows.shape) == (N,), "rows must be int64 [N]")
+    else:
+        require(N <= R, "more mask rows than data rows")
+    check(lib().vipe_convex_upsample(ptr(mask), DTYPE_CODE[mask.dtype], ptr(data), ptr(out), ptr(rows), N, R, h, w, C,
+                                     stream_ptr(data)), "convex_upsample")
+    return out

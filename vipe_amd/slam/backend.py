@@ -28,6 +28,7 @@ class BackendArgs:
 
 class SLAMBackend:
     depth_model = None
+    upsample = False  # handed to every graph `run` builds (FactorGraph.upsample: full-resolution keyframe disparities)
 
     def __init__(self, update_module, video, args: BackendArgs, device):
         self.net, self.video, self.args, self.device = update_module, video, args, device
@@ -40,6 +41,8 @@ class SLAMBackend:
         t = self.video.n_frames
         graph = FactorGraph(self.net, self.video, self.device, max_factors=16 * t, incremental=False,
                             cross_view=a.cross_view)
+        if self.upsample:
+            graph.upsample = True
         graph.add_proximity_factors(rad=a.backend_radius, nms=a.backend_nms, thresh=a.backend_thresh, beta=a.beta)
         if a.adaptive_cross_view:
             self.video.build_adaptive_cross_view_idx()

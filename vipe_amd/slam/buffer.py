@@ -31,7 +31,7 @@ def fold_flow_terms(target, weight, target2, weight2):
 
 class GraphBuffer:
     def __init__(self, height, width, n_views=1, buffer_size=1024, init_disp=1.0, cross_view_idx=None,
-                 ba_config=None, camera_type="pinhole", device=torch.device("cuda")):
+                 ba_config=None, camera_type="pinhole", device=torch.device("cuda"), upsample_disps=False):
         assert height % 8 == 0 and width % 8 == 0  # buffer.py:76
         if cross_view_idx is None:
             cross_view_idx = [(i + 1) % n_views for i in range(n_views)]
@@ -52,6 +52,14 @@ class GraphBuffer:
         self.disps = torch.ones(buffer_size, n_views, ht, wd, **f32) * init_disp
         self.disps_sens = torch.zeros(buffer_size, n_views, ht, wd, **f32)
         self.masks = torch.zeros(buffer_size, n_views, ht, wd, device=device, dtype=torch.bool)
+        # Full-resolution keyframe disparities (opt-in, not in the reference: DROID-SLAM's `disps_up`): written by
+        # `FactorGraph.update` / `update_batch` with `upsample` set, from `disps` and the operator's convex-combination
+        # mask (droid_net_ext.cvx_upsample).  4 * V * H * W bytes per slot - 0.8 GB at 1024 x 384 x 512 - so nothing is
+        # allocated unless asked for.  `disps_up_valid`: the slot has been written since it was (re)used.
+        self.disps_up = self.disps_up_valid = None
+        if upsample_disps:
+            self.disps_up = torch.zeros(buffer_size, n_views, height, width, **f32)
+            self.disps_up_valid = torch.zeros(buffer_size, n_views, device=device, dtype=torch.bool)
         self._images = None  # full-resolution RGB 0-1 fp16 [N,V,3,H,W] (buffer.py:81-89), allocated on first use
         self.fmaps = torch.zeros(buffer_size, n_views, 128, ht, wd, device=device, dtype=torch.half)
         self.nets = torch.zeros(buffer_size, n_views, 128, ht, wd, device=device, dtype=torch.half)
@@ -86,6 +94,10 @@ class GraphBuffer:
     @property
     def flattened_disps_sens(self):
         return self.disps_sens.view(-1, *self.disps_sens.shape[2:])
+
+    @property
+    def flattened_disps_up(self):
+        return None if self.disps_up is None else self.disps_up.view(-1, *self.disps_up.shape[2:])
 
     @property
     def flattened_fmaps(self):
@@ -198,12 +210,14 @@ class GraphBuffer:
         assert ix == self.n_frames - 2
         self.touch()
         for name in ("tstamp", "_images", "poses", "disps", "disps_sens", "nets", "inps", "fmaps", "masks",
-                     "cross_view_idx"):
+                     "cross_view_idx", "disps_up", "disps_up_valid"):
             arr = getattr(self, name, None)
             if arr is not None:
                 arr[ix] = arr[ix + 1]
         if getattr(self, "dirty", None) is not None:
             self.dirty[ix] = True
+        if self.disps_up_valid is not None:
+            self.disps_up_valid[ix + 1] = False  # the freed slot: whatever keyframe takes it next has not been upsampled
         self.n_frames -= 1
 
     def update_disps_sens(self, depth_model, frame_idx=None):

@@ -199,6 +199,12 @@ def _index_property(name):
 
 
 class FactorGraph:
+    # Opt-in (not in the reference, which discards the operator's upsampling mask: factor_graph.py:269): after every BA
+    # of `update` - and after the last one of `update_batch` - the disparities the BA has just produced are upsampled to
+    # full resolution with THIS iteration's mask into `buffer.disps_up` (DROID-SLAM's order; `_upsample_disps`).  Needs
+    # `GraphBuffer(upsample_disps=True)`.  Off: not one launch, allocation or argument differs.
+    upsample = False
+
     def __init__(self, update_module, buffer, device, max_factors=48, incremental=True, cross_view=False):
         self.update_op = update_module
         self.buffer = buffer
@@ -502,6 +508,16 @@ class FactorGraph:
         self.target_inac, self.weight_inac = cap[0][:, :n + k], cap[1][:, :n + k]
         return cap[0], cap[1], n
 
+    def _upsample_disps(self, mask, du):
+        """mask [n_src,h,w,576] f16 of the operator (row s belongs to source slot du[s], as `eta` does in update_finish)
+        -> buffer.disps_up[du] = convex upsampling of buffer.disps[du], read and written in place through the flattened
+        (frame * V + view) rows: no gathers.  `droid_net_ext.cvx_upsample` is the only route to the kernel."""
+        from ..ext import droid_net_ext
+        buf = self.buffer
+        require(buf.disps_up is not None, "FactorGraph.upsample needs GraphBuffer(upsample_disps=True)")
+        droid_net_ext.cvx_upsample(buf.flattened_disps[..., None], mask, rows=du, out=buf.flattened_disps_up[..., None])
+        buf.disps_up_valid.view(-1)[du] = True
+
     def _shift_plan(self, plan5, base):
         """(pi, qi, di, pj, qj) -> the same relative to keyframe `base` (+ base), see GraphBuffer.bundle_adjustment"""
         pi, qi, di, pj, qj = plan5
@@ -536,9 +552,10 @@ class FactorGraph:
         # the lookup is deferred into the correlation encoder's first convolution (one kernel, no [E,h,w,200] tensor); the
         # whole operator is one natively sequenced library call
         corr = self.corr.lookup_deferred(coords1)
-        self.net_n, dw, eta, _ = eng.forward_nhwc(self.net_n, self.xbuf, corr, motn, ix=P["dix"], n_src=P["n_src"],
-                                                  net_out=self._net_spare(), csr=P["csr"], pgate=self.pgate,
-                                                  gate_state=self._gate_state)
+        up = {"want_upmask": True} if self.upsample else {}  # the mask head on the persistent a2: one more 1x1 conv
+        self.net_n, dw, eta, upmask = eng.forward_nhwc(self.net_n, self.xbuf, corr, motn, ix=P["dix"], n_src=P["n_src"],
+                                                       net_out=self._net_spare(), csr=P["csr"], pgate=self.pgate,
+                                                       gate_state=self._gate_state, **up)
         self._gate_state = None
         # The new hidden state is final here, and the dense BA below keeps ONE workgroup busy for most of its time
         # (band Cholesky): everything of the next iteration's gates that depends on the hidden state alone - the
@@ -614,6 +631,8 @@ class FactorGraph:
         buf.bundle_adjustment(target.view(E, -1, 2), weight.view(E, -1, 2), self.damping, ii, jj, t0,
                               t1 if not fixed_motion else t0, itrs, 1e-3, 0.1, motion_only, limited_disp, False, False,
                               plan=plan, ba_state=self._ba_state, plan_key=plan_key, overlap=ba_overlap)
+        if self.upsample:  # after the BA: this iteration's mask on the disparities it has just produced
+            self._upsample_disps(upmask, P["du"])
         if overlap:
             main.wait_stream(self._side)
             self._gate_state = gate_state
@@ -696,7 +715,11 @@ class FactorGraph:
             return c
 
         vols, kept_rows = {}, 0
-        for _ in range(steps):
+        for step in range(steps):
+            # the last pass's masks are kept per chunk until its BA has run ([n_src,h,w,576] f16 each: 3.5 MB per source
+            # keyframe and view at 48 x 64); earlier passes do not ask for them
+            up = {"want_upmask": True} if self.upsample and step == steps - 1 else {}
+            upmasks = []
             coords1, motn = slam_ext.reproject_motion_nhwc(buf.poses, buf.flattened_disps, buf.intrinsics, buf.rig,
                                                            P["pi"], P["qi"], P["pj"], P["qj"], P["di"],
                                                            self.target[0].contiguous(), camera=buf.camera_type)
@@ -722,8 +745,11 @@ class FactorGraph:
                     corr1 = corr_op(c1[None], c["dis"], c["djs"])  # [1,n,196,h,w] fp32
                     corr_n = torch.zeros((n, self.ht, self.wd, 200), dtype=torch.half, device=self.device)
                     corr_n[..., :196] = corr1[0].permute(0, 2, 3, 1)
-                net, dw, eta, _ = eng.forward_nhwc(take(self.net_n).contiguous(), c["xb"], corr_n, take(motn).contiguous(),
-                                                   ix=c["dixs"], n_src=c["n_src"], csr=c["csr"], pgate=c["pgate"])
+                net, dw, eta, upmask = eng.forward_nhwc(take(self.net_n).contiguous(), c["xb"], corr_n,
+                                                        take(motn).contiguous(), ix=c["dixs"], n_src=c["n_src"],
+                                                        csr=c["csr"], pgate=c["pgate"], **up)
+                if up:
+                    upmasks.append((upmask, c["du"]))
                 WORK["edge_updates"] += n
                 self._gate_state = None
                 if whole:
@@ -741,3 +767,5 @@ class FactorGraph:
             buf.bundle_adjustment(self.target.view(E, -1, 2), self.weight.view(E, -1, 2), self.damping, self.ii, self.jj,
                                   1, t, itrs, 1e-5, 1e-2, False, False, optimize_intrinsics, optimize_rig_rotation,
                                   verbose=solver_verbose)
+            for upmask, du in upmasks:
+                self._upsample_disps(upmask, du)

@@ -75,10 +75,17 @@ class SLAMMap:
 
 class SLAMOutput:
     """interface.py:143-163: what `SLAMSystem.run` returns - trajectory (camera -> world per frame, SE3 [N]), intrinsics
-    [V,4], the rig, the map, the BA residual."""
+    [V,4], the rig, the map, the BA residual.
 
-    def __init__(self, *, trajectory, intrinsics, rig=None, slam_map=None, ba_residual=0.0):
+    Not in the reference, None unless `SLAMConfig.upsample_disps`: `keyframe_disps_up` [N_kf,V,H,W] f32, the keyframes'
+    disparities at full SLAM resolution (the 1/8 maps through the update operator's learned convex upsampling, DROID-SLAM's
+    `disps_up`), and `keyframe_disps_up_valid` [N_kf,V] bool, both aligned with `keyframe_ids`.  H x W is the resolution
+    SLAM ran at: for `run(..., native_resolution=True)` the resized and cropped size, not the native one."""
+
+    def __init__(self, *, trajectory, intrinsics, rig=None, slam_map=None, ba_residual=0.0, keyframe_disps_up=None,
+                 keyframe_disps_up_valid=None):
         self.trajectory, self.intrinsics, self.rig, self.slam_map, self.ba_residual = trajectory, intrinsics, rig, slam_map, ba_residual
+        self.keyframe_disps_up, self.keyframe_disps_up_valid = keyframe_disps_up, keyframe_disps_up_valid
 
     @property
     def keyframe_ids(self):

@@ -48,6 +48,9 @@ class SLAMConfig:
     release_cached_memory: bool = False  # several clips share this card (one process each): hand the global BA's pyramid
                                          # blocks (~100 GB at 200 keyframes) back to the driver after the second backend pass
                                          # instead of keeping them cached for the next clip of this process
+    upsample_disps: bool = False   # full-resolution keyframe disparities (`SLAMOutput.keyframe_disps_up`): the operator's
+                                   # convex-upsampling mask applied after every BA of the frontend and after the last
+                                   # one of every backend pass; 4 * V * H * W bytes per buffer slot.  Off: nothing changes
     backend_lock_path: str = None        # ... and let their global-BA phases - each fills the chip by itself and wants the
                                          # pyramid budget to itself - take turns (an advisory file lock held around the two
                                          # backend passes), while the other clips' pass 1 / pass 2 run beside it
@@ -80,7 +83,8 @@ class SLAMSystem:
     def _build_components(self, height, width, n_views, rig, camera_type):
         c = self.config
         self.buffer = GraphBuffer(height, width, n_views=n_views, buffer_size=c.buffer, init_disp=c.init_disp,
-                                  cross_view_idx=c.cross_view_idx, camera_type=camera_type, device=self.device)
+                                  cross_view_idx=c.cross_view_idx, camera_type=camera_type, device=self.device,
+                                  **({"upsample_disps": True} if c.upsample_disps else {}))
         self.buffer.rig[:] = rig.data.to(self.device)
         self.buffer.sparse_tracks = self.sparse_tracks
         self.motion_filter = self.motion_filter_cls(self.droid_net, sparse_tracks=self.sparse_tracks, thresh=c.filter_thresh,
@@ -88,6 +92,8 @@ class SLAMSystem:
         self.frontend = SLAMFrontend(self.droid_net.update, self.buffer, c.frontend, self.device)
         self.backend = SLAMBackend(self.droid_net.update, self.buffer, c.backend, self.device)
         self.inner_filler = InnerFiller(self.droid_net.update, self.buffer, c.infill, self.device)
+        if c.upsample_disps:  # the keyframe graphs; InnerFiller's stays off (non-keyframe depth is not upsampled)
+            self.frontend.graph.upsample = self.backend.upsample = True
         if self.metric_depth is not None:
             assert n_views == 1, "the global scale lies in the null space of a multi-view problem (system.py:115-118)"
         self.backend.depth_model = self.metric_depth
@@ -256,7 +262,11 @@ class SLAMSystem:
         given at the native size and `SLAMOutput.intrinsics` come back recovered to it (system.py:306-309).  A
         `sparse_tracks` tracker is handed the frames as they came (`track_image`), while the reference's sees the
         resized, cropped ones: in native mode its `observations` must be in `StandardResize(...).out_size` pixel
-        coordinates (resize its input, or map its tracks with `forward_intrinsics`' scale and crop) - not converted here."""
+        coordinates (resize its input, or map its tracks with `forward_intrinsics`' scale and crop) - not converted here.
+
+        With `SLAMConfig.upsample_disps` the output carries `keyframe_disps_up` [N_kf,V,H,W] and
+        `keyframe_disps_up_valid` [N_kf,V] (aligned with `keyframe_ids`), at SLAM resolution: with native_resolution=True
+        that is the resized and cropped size (`StandardResize(...).out_size`), not the native one."""
         frames = [f if isinstance(f, (list, tuple)) else [f] for f in frames]
         total, n_views = len(frames), len(frames[0])
         assert total > 0 and all(len(f) == n_views for f in frames)
@@ -292,4 +302,8 @@ class SLAMSystem:
         intrinsics = b.intrinsics.clone()
         if resizes is not None:
             intrinsics = torch.stack([r.recover_intrinsics(intrinsics[v]) for v, r in enumerate(resizes)])
-        return SLAMOutput(trajectory=filled.poses.inv(), intrinsics=intrinsics, rig=SE3(b.rig.clone()), slam_map=slam_map)
+        up = {}
+        if b.disps_up is not None:  # slots [0, n_frames) are the keyframes again (InnerFiller.compute), in keyframe_ids' order
+            up = dict(keyframe_disps_up=b.disps_up[:b.n_frames].clone(),
+                      keyframe_disps_up_valid=b.disps_up_valid[:b.n_frames].clone())
+        return SLAMOutput(trajectory=filled.poses.inv(), intrinsics=intrinsics, rig=SE3(b.rig.clone()), slam_map=slam_map, **up)
