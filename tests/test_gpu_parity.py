@@ -1876,6 +1876,53 @@ def test_dense_window_solver_with_two_intrinsics_columns():
     assert np.abs(k - ok_).max() <= 1e-4 * np.abs(ok_).max()
 
 
+def band_solver_form(info, two_chain=True):
+    """The run-time selection of `ba_solve_band_kernel` restated from info[0] (free poses), info[3] (unknowns) and info[4]
+    (band width in 6 x 6 blocks): "two_chain" (long pose-only chains, both ends at once), "narrow" (`band_solve_body<2, false>`)
+    or "wide" (`band_solve_body<BAND_UPT, true>`: two band columns per lane, six trailing-update pairs per thread).  Together
+    with info[5] == 1 (the band solver took the system) it pins a case to the form it was written for."""
+    nb, n, bandblk = int(info[0]), int(info[3]), int(info[4])
+    F = n - 6 * nb
+    assert 0 <= F <= 2, f"the band solver takes at most two intrinsics columns, not {F}"
+    PB = 6 * bandblk
+    npair = PB * (PB + 1) // 2 + (F + 1) * PB + (0, 2, 5)[F]
+    wide = PB + 7 > 64 or npair > 917  # 917 = 21 + 2 * (512 - 64): the pairs two slots per thread hold
+    if not wide and F == 0 and two_chain and bandblk >= 1 and nb >= 4 * bandblk + 4:
+        return "two_chain"
+    return "wide" if wide else "narrow"
+
+
+@pytest.mark.parametrize("n,radius,cam,intr,form,PB", [
+    (8, 2, "pinhole", False, "narrow", 24),   # one chain (7 free poses < 4 * 4 + 4), no tail column
+    (14, 2, "pinhole", True, "narrow", 24),   # one tail column (focal length)
+    (14, 2, "mei", True, "narrow", 24),       # two tail columns (focal length, distortion): all five tail-tail pairs
+    (13, 12, "mei", True, "wide", 66),        # second band column in use, two tail columns: 2211 + 198 + 5 pairs
+    (9, 8, "pinhole", True, "wide", 42),      # wide by the pair count alone (903 + 84 + 2 > 917), one band column
+])
+def test_band_solver_forms_against_fp64_oracle(n, radius, cam, intr, form, PB):
+    """The one-chain forms of the LDS band solver that no other case pins: the narrow instantiation with 0 / 1 / 2
+    intrinsics columns (pose-pose, tail-pose and tail-tail trailing pairs, the unblocked tail columns, the tail part of the
+    back substitution), the wide one with two tail columns, and the wide one chosen by the pair count with a band that
+    still fits one wave.  Each case asserts that the band solver took the system in the intended form (a system the band
+    solver declines is solved by the LDS dense solver all the same), then HIP fp32 vs the fp64 oracle."""
+    g = make_graph(n=n, height=96, width=128, radius=radius, seed=200 + n + radius)
+    k0 = g.intrinsics if cam == "pinhole" else np.concatenate([g.intrinsics, np.array([[0.4]], np.float32)], 1)
+    bk = dict(t0=1, t1=n, n_iters=2, pose_damping=1e-3, pose_ep=0.1, motion_only=False, limited_disp=False,
+              optimize_intrinsics=intr)
+    p, d, k, info = run_hip_ba(g, k0, cam, bk)
+    E = len(g.ii)
+    op, od, ok_, _ = oba.bundle_adjustment(g.poses, g.disps[:, None], g.disps_sens[:, None], k0, ose3.se3_identity(1),
+                                           g.target.reshape(E, -1, 2), g.weight.reshape(E, -1, 2), g.eta[:, None], g.ii, g.jj,
+                                           model=cam, **bk)
+    F = (2 if cam == "mei" else 1) if intr else 0
+    assert info[0] == n - 1 and info[3] == 6 * (n - 1) + F and 6 * info[4] == PB
+    assert info[5] == 1 and info[2] == 0 and band_solver_form(info) == form
+    assert np.abs(p - op).max() <= 1e-4 * max(1.0, np.abs(op).max())
+    assert np.abs(d - od[:, 0]).max() <= 1e-4 * np.abs(od).max()
+    if intr:
+        assert np.abs(k - ok_).max() <= 1e-4 * np.abs(ok_).max()
+
+
 @pytest.mark.parametrize("intr", [False, True])
 def test_dense_ba_dense_window_of_twelve_poses(intr):
     """The frontend's steady state (12 free poses, every pair coupled, source degree 12): the reduced system is a dense
@@ -1891,6 +1938,8 @@ def test_dense_ba_dense_window_of_twelve_poses(intr):
                                            ose3.se3_identity(1), g.target.reshape(E, -1, 2), g.weight.reshape(E, -1, 2),
                                            g.eta[:, None], g.ii, g.jj, **bk)
     assert info[0] == 12 and info[2] == 0
+    # the band solver took it, in the wide form with the second band column in use (PB = 66 > 64)
+    assert info[5] == 1 and 6 * info[4] == 66 and band_solver_form(info) == "wide"
     assert np.abs(p - op).max() <= 1e-4 * max(1.0, np.abs(op).max())
     assert np.abs(d - od[:, 0]).max() <= 1e-4 * np.abs(od).max()
     if intr:
@@ -2522,7 +2571,7 @@ def test_sparse_tracks_target_weight_matches_oracle():
 
 
 @pytest.mark.parametrize("n,radius", [(48, 3), (33, 2), (34, 1), (40, 3)])
-def test_two_chain_band_solve_equals_one_chain(n, radius, monkeypatch):
+def test_two_chain_band_solve_equals_one_chain(n, radius):
     """Long pose-only neighbourhood chains are eliminated from both ends at once (band2_solve_body: chain A in natural order,
     chain B mirrored, the separator's Schur contributions merged, separator factored, both chains back-substituted in
     parallel).  Same fp64 arithmetic on another elimination order: poses / disparities agree with the one-chain form
@@ -2536,6 +2585,7 @@ def test_two_chain_band_solve_equals_one_chain(n, radius, monkeypatch):
         res[flag] = run_hip_ba(g, g.intrinsics, "pinhole", dict(bk, solver_options=0 if flag == "1" else 1))
     (p1, d1, _, i1), (p0, d0, _, i0) = res["1"], res["0"]
     assert i1[2] == 0 and i0[2] == 0 and i1[5] == 1 and i0[5] == 1  # no failed pivot; the LDS band solver took both
+    assert band_solver_form(i1) == "two_chain" and band_solver_form(i0, two_chain=False) == "narrow"
     # (fp32 states; the accumulate kernels' atomics alone make two runs of ONE form differ in the last bits)
     assert np.abs(p1 - p0).max() <= 1e-5 * max(1.0, np.abs(p0).max()) and np.abs(d1 - d0).max() <= 1e-5 * np.abs(d0).max()
     assert np.abs(p0 - g.poses).max() > 1e-4  # the step moved the poses

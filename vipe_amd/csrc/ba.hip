@@ -21,12 +21,16 @@
 //
 // One translation unit in parts, included below in this order inside the one anonymous namespace (the kernels take
 // BAArgs by value and have internal linkage):
-//   ba_common.cuh        constants, BAWs / BAArgs, carve, load_tw, valid_weight, term_setup, finish_disp, s_add
+//   ba_common.cuh        constants, BAWs / BAArgs, carve, load_tw, valid_weight, term_setup, finish_disp, s_add, rsqrt_nr and
+//                        what the four solvers share: readlane_f64, tri_index, damped_diag, store_step, apply_retraction
 //   ba_plan.inc          ba_sens_kernel, ba_plan_kernel
 //   ba_accumulate.inc    the term walk written once (term_setup_m, walk_pixel, term_point_jacobians, walk_tile, gram_r1,
 //                        flush_term_blocks, flush_frame_blocks, store_disp_block), then the three accumulate kernels
 //                        that call it and ba_schur_kernel
-//   ba_solve_band.inc    retraction + ba_solve_band_kernel        ba_solve_dense.inc   ba_solve_dense_kernel
+//   ba_solve_band.inc    the block step over one LDS band image written once (BandImage: band_factor_diag, band_load_rows,
+//                        BandPairs / band_pairs_setup, band_panel, band_trailing, band_backsub_block), the one-chain and
+//                        two-chain bodies that call it, ba_solve_band_kernel
+//   ba_solve_dense.inc   ba_solve_dense_kernel
 //   ba_solve_global.inc  ba_solve_kernel + the tiled Cholesky     ba_retract.inc       ba_retract_kernel, clamp_min_kernel
 // This file keeps the overlap protocol, run_iters and the exported entry points.
 //

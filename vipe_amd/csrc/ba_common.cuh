@@ -162,3 +162,73 @@ __device__ __forceinline__ double rsqrt_nr(double x) {
   r = r * __builtin_fma(-hx * r, r, 1.5);
   return r;
 }
+
+// ---- shared by the four solvers (LDS band, LDS dense, global memory, tiled)
+
+__device__ __forceinline__ double readlane_f64(double v, int lane) {
+  const unsigned long long u = __builtin_bit_cast(unsigned long long, v);
+  const unsigned lo = (unsigned)__builtin_amdgcn_readlane((int)u, lane);
+  const unsigned hi = (unsigned)__builtin_amdgcn_readlane((int)(u >> 32), lane);
+  return __builtin_bit_cast(double, ((unsigned long long)hi << 32) | lo);
+}
+
+// (i, j), j <= i, of the lower-triangle entry with linear index q = i (i + 1) / 2 + j
+__device__ __forceinline__ void tri_index(int q, int& i, int& j) {
+  i = (int)((sqrtf(8.0f * (float)q + 1.0f) - 1.0f) * 0.5f);
+  while ((i + 1) * (i + 2) / 2 <= q) ++i;
+  while (i * (i + 1) / 2 > q) --i;
+  j = q - i * (i + 1) / 2;
+}
+
+// LM damping of the diagonal entry v of row r (matrix.py:179-186): v + ep + lambda * diag(H).  Pose rows (r < npr): the
+// caller's (lambda, ep); intrinsics rows 1e-6 / 1e-6; rig-rotation rows 1e-4 / 1e-4 (buffer.py:466,498,503).  hd = Hd[r],
+// loaded by the caller (the LDS solvers preload it with the matrix entries); DROID damps with the reduced diagonal itself
+// (geom_kernels.cu:1176) and does not read it.
+__device__ __forceinline__ double damped_diag(const BAArgs& a, int r, int npr, double v, double hd) {
+  const bool pose = r < npr, rigrow = a.mv && r >= npr + a.nintr;
+  const double ep = pose ? (double)a.p.pose_ep : (rigrow ? 1e-4 : 1e-6);
+  const double lam = pose ? (double)a.p.pose_damping : (rigrow ? 1e-4 : 1e-6);
+  return v + (ep + lam * (a.droid ? v : hd));
+}
+
+// the step of unknown dd as float; zero after a failed pivot (`bad`) and for a NaN
+__device__ __forceinline__ void store_step(const BAWs& w, int dd, double x, bool bad) {
+  if (bad || !(x == x)) x = 0.0;
+  w.dx[dd] = (float)x;
+}
+
+// Retraction shared by the four solvers: poses X <- Exp(dx) X (retractor.py:27-29), intrinsics (retractor.py:50-62)
+__device__ __forceinline__ void apply_retraction(const BAArgs& a, int t, int nthreads, int n_free) {
+  const BAWs& w = a.w;
+  for (int sl = t; sl < n_free; sl += nthreads) {
+    const int pidx = w.slot_pose[sl];
+    float xi[6];
+    for (int q = 0; q < 6; ++q) xi[q] = w.dx[6 * sl + q];
+    lie::SE3<float> X(a.poses + 7 * pidx);
+    (lie::SE3<float>::exp(xi) * X).store(a.poses + 7 * pidx);
+  }
+  if (a.mv) {
+    // one intrinsics block per view (retractor.py:50-62 with len(dx) == V) and one rotation-only step per view >= 1
+    // (retractor.py:32-37: the translation part of the tangent is zeroed, X <- Exp([0, phi]) X)
+    const int F = 1 + a.D, V = a.p.n_views;
+    if (a.p.optimize_intrinsics && t < V) {
+      float* I = a.intr + t * (4 + a.D);
+      const float df = w.dx[6 * n_free + t * F];
+      I[0] += df; I[1] += df;
+      if (F > 1) I[4] += 0.01f * w.dx[6 * n_free + t * F + 1];
+    }
+    if (a.p.optimize_rig_rotation && t >= 1 && t < V) {
+      float xi[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+      for (int q = 3; q < 6; ++q) xi[q] = w.dx[6 * n_free + a.nintr + 6 * (t - 1) + q];
+      lie::SE3<float> X(a.rig + 7 * t);
+      (lie::SE3<float>::exp(xi) * X).store(a.rig + 7 * t);
+    }
+  } else if (a.p.optimize_intrinsics && t == 0) {
+    const int F = 1 + a.D;
+    const float df = w.dx[6 * n_free];
+    for (int vq = 0; vq < a.p.n_views; ++vq) {
+      float* I = a.intr + vq * (4 + a.D);
+      if (I[0] > 0) { I[0] += df; I[1] += df; if (F > 1) I[4] += 0.01f * w.dx[6 * n_free + 1]; }
+    }
+  }
+}

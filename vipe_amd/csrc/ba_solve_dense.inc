@@ -28,7 +28,6 @@ typedef double double4c __attribute__((ext_vector_type(4)));
 __global__ __launch_bounds__(DN_T) void ba_solve_dense_kernel(BAArgs a, int lds_doubles) {
   extern __shared__ __align__(16) unsigned char smem_raw[];
   double* const L = reinterpret_cast<double*>(smem_raw);
-  const vipe_ba_params& prm = a.p;
   const BAWs& w = a.w;
   const int t = threadIdx.x;
   const int n = w.info[3], n_free = w.info[0];
@@ -74,10 +73,6 @@ __global__ __launch_bounds__(DN_T) void ba_solve_dense_kernel(BAArgs a, int lds_
   twave = __builtin_amdgcn_readfirstlane(twave);
   __syncthreads();
   for (int i = t; i < DN_PP * 16 * NTR; i += DN_T) Pbuf[i] = 0.0;  // columns 6, 7 stay zero; rows beyond n too
-  auto damped = [&](int r, double v) {  // LM damping on the diagonal (matrix.py:179-186)
-    const bool pose = r < npr;
-    return v + (pose ? (double)prm.pose_ep : 1e-6) + (pose ? (double)prm.pose_damping : 1e-6) * (a.droid ? v : w.Hd[r]);
-  };
 
   // ---- tile waves: tile tau = I (I + 1) / 2 + J of the lower triangle -> tile wave tau % 6, slot tau / 6.  Per slot and
   //      lane: T (four entries: rows 16 I + kq + 4 r4, column 16 J + l16, NEGATED), the row / column this lane extracts
@@ -93,10 +88,8 @@ __global__ __launch_bounds__(DN_T) void ba_solve_dense_kernel(BAArgs a, int lds_
 #pragma unroll
     for (int sl = 0; sl < DN_SLOTS; ++sl) {
       const int tau = twave + 6 * sl;
-      int ti = (int)((sqrtf(8.0f * (float)tau + 1.0f) - 1.0f) * 0.5f);
-      while ((ti + 1) * (ti + 2) / 2 <= tau) ++ti;
-      while (ti * (ti + 1) / 2 > tau) --ti;
-      const int tj = tau - ti * (ti + 1) / 2;
+      int ti, tj;
+      tri_index(tau, ti, tj);
       const bool ok = tau < NTL;
       colv[sl] = ok ? 16 * tj + l16 : -(1 << 20);  // an absent tile is never live and never intersects a column block
       rowv[sl] = ok ? 16 * ti + kq : -(1 << 20);
@@ -119,10 +112,7 @@ __global__ __launch_bounds__(DN_T) void ba_solve_dense_kernel(BAArgs a, int lds_
       for (int r4 = 0; r4 < 4; ++r4) {
         const int row = rowv[sl] + 4 * r4, col = colv[sl];
         double v = T[sl][r4];
-        if (col == row) {
-          const bool pose = row < npr;
-          v += (pose ? (double)prm.pose_ep : 1e-6) + (pose ? (double)prm.pose_damping : 1e-6) * (dr ? v : hd[r4]);
-        }
+        if (col == row) v = damped_diag(a, row, npr, v, hd[r4]);  // LM damping on the diagonal
         T[sl][r4] = (row <= n && col < n && col <= row && col >= 0) ? -v : 0.0;
       }
     }
@@ -149,7 +139,13 @@ __global__ __launch_bounds__(DN_T) void ba_solve_dense_kernel(BAArgs a, int lds_
       double v = (c == ic) ? 1.0 : 0.0;
       if (ic < bw0 && c <= ic) {
         v = S[(int64_t)ic * ld + c];
-        if (c == ic) v = damped(ic, v);
+        if (c == ic) {
+          // LM damping, summed as (v + ep) + lambda * d: damped_diag adds v + (ep + lambda * d), one rounding apart,
+          // and this block's factor is the head of the dependent chain - its bits stay what they were
+          const bool pose = ic < npr;
+          v = v + (pose ? (double)a.p.pose_ep : 1e-6) +
+              (pose ? (double)a.p.pose_damping : 1e-6) * (a.droid ? v : w.Hd[ic]);
+        }
       }
       A[c] = v;
     }
@@ -471,11 +467,7 @@ __global__ __launch_bounds__(DN_T) void ba_solve_dense_kernel(BAArgs a, int lds_
 #pragma unroll
       for (int q = 0; q < YR; ++q) {
         const int dd = 48 * q + t;
-        if (dd < n) {
-          double x = yv[q];
-          if (bad || !(x == x)) x = 0.0;
-          w.dx[dd] = (float)x;
-        }
+        if (dd < n) store_step(w, dd, yv[q], bad);
       }
     }
     if (t == 0) {

@@ -21,13 +21,10 @@ struct SolveLds {
   int fail;
 };
 
-
-
 __global__ __launch_bounds__(SOLVE_T) void ba_solve_kernel(BAArgs a, int panel_cap) {
   extern __shared__ __align__(16) unsigned char smem_raw[];
   SolveLds& sh = *reinterpret_cast<SolveLds*>(smem_raw);
   double* PT = reinterpret_cast<double*>(smem_raw + ((sizeof(SolveLds) + 15) / 16) * 16);  // [NB][panel_cap]
-  const vipe_ba_params& prm = a.p;
   const BAWs& w = a.w;
   const int t = threadIdx.x;
   const int n = w.info[3], n_free = w.info[0];
@@ -35,13 +32,10 @@ __global__ __launch_bounds__(SOLVE_T) void ba_solve_kernel(BAArgs a, int panel_c
   double* S = w.S;
   if (t == 0) sh.fail = 0;
   if (n == 0 || w.info[5] != 0 || n > CT_MIN_N) return;  // an LDS solver (band: 1, dense: 2) took the system; large ones: tiled
-  // LM damping on the diagonal: += ep + lambda * diag(H)  (matrix.py:179-186)
+  // LM damping on the diagonal
   for (int dd = t; dd < n; dd += SOLVE_T) {
-    // poses: the caller's (lambda, ep); intrinsics 1e-6 / 1e-6; rig rotations 1e-4 / 1e-4 (buffer.py:466,498,503)
-    const bool pose = dd < 6 * n_free, rigrow = a.mv && dd >= 6 * n_free + a.nintr;
-    const double ep = pose ? (double)prm.pose_ep : (rigrow ? 1e-4 : 1e-6);
-    const double lam = pose ? (double)prm.pose_damping : (rigrow ? 1e-4 : 1e-6);
-    S[(int64_t)dd * ld + dd] += ep + lam * (a.droid ? S[(int64_t)dd * ld + dd] : w.Hd[dd]);
+    double& sdd = S[(int64_t)dd * ld + dd];
+    sdd = damped_diag(a, dd, 6 * n_free, sdd, a.droid ? 0.0 : w.Hd[dd]);
   }
   __syncthreads();
   const bool use_lds_panel = (n + 1) <= panel_cap;
@@ -133,10 +127,8 @@ __global__ __launch_bounds__(SOLVE_T) void ba_solve_kernel(BAArgs a, int panel_c
       const int nt = (m + 15) >> 4;
       const int ntiles = nt * (nt + 1) / 2;
       for (int q = wv; q < ntiles; q += SOLVE_T / 64) {
-        int ti = (int)((sqrtf(8.0f * (float)q + 1.0f) - 1.0f) * 0.5f);
-        while ((ti + 1) * (ti + 2) / 2 <= q) ++ti;
-        while (ti * (ti + 1) / 2 > q) --ti;
-        const int tj = q - ti * (ti + 1) / 2;
+        int ti, tj;
+        tri_index(q, ti, tj);
         double4v c = {0.0, 0.0, 0.0, 0.0};
         const int ar = 16 * ti + (ln & 15), bc = 16 * tj + (ln & 15), kq = ln >> 4;
 #pragma unroll
@@ -255,11 +247,7 @@ __global__ __launch_bounds__(SOLVE_T) void ba_solve_kernel(BAArgs a, int panel_c
   }
   const bool bad = sh.fail != 0;
   if (t == 0 && bad) w.info[2] += 1;
-  for (int dd = t; dd < n; dd += SOLVE_T) {
-    double x = yrow[dd];
-    if (bad || !(x == x)) x = 0.0;  // zero step on a failed factorisation
-    w.dx[dd] = (float)x;
-  }
+  for (int dd = t; dd < n; dd += SOLVE_T) store_step(w, dd, yrow[dd], bad);
   __syncthreads();
   apply_retraction(a, t, SOLVE_T, n_free);
 }
@@ -305,7 +293,6 @@ __global__ __launch_bounds__(256) void chol_potrf_kernel(BAArgs a, int k) {
   if (c0 >= n) return;
   const int bw = min(CT, n - c0);
   const BAWs& w = a.w;
-  const vipe_ba_params& prm = a.p;
   const int ld = w.ld, t = threadIdx.x, lane = t & 63, wave = t >> 6;
   double* S = w.S;
   __shared__ double Ls[CT][CT + 1];   // the factor tile (lower), identity beyond bw
@@ -314,8 +301,8 @@ __global__ __launch_bounds__(256) void chol_potrf_kernel(BAArgs a, int k) {
   if (t == 0) fail = 0;
   if (k == 0 && t == 0) w.info[7] = 0;  // failure flag of this factorisation
   __syncthreads();
-  // the tile travels global <-> LDS with all 256 threads (row segments, coalesced), LM damping (matrix.py:179-186: poses
-  // (lambda, ep); intrinsics 1e-6; rig rotations 1e-4) added on the way in.  The last tile column of a system with
+  // the tile travels global <-> LDS with all 256 threads (row segments, coalesced), LM damping (damped_diag) added on the
+  // way in.  The last tile column of a system with
   // n % 64 != 0 shares its tile row with the rhs (row n = c0 + bw): row bw of the tile carries it through the
   // factorisation as one more row below the diagonal (its own "diagonal" entry is a dummy 1).
   const bool has_rhs = bw < CT && c0 + bw == n;
@@ -332,13 +319,7 @@ __global__ __launch_bounds__(256) void chol_potrf_kernel(BAArgs a, int k) {
 #pragma unroll
     for (int q = 0; q < 16; ++q) {
       const int i = t + 256 * q, r = i >> 6, c = i & 63;
-      if (r < bw && c == r) {
-        const int g = c0 + r;
-        const bool pose = g < 6 * n_free, rigrow = a.mv && g >= 6 * n_free + a.nintr;
-        const double ep = pose ? (double)prm.pose_ep : (rigrow ? 1e-4 : 1e-6);
-        const double lam = pose ? (double)prm.pose_damping : (rigrow ? 1e-4 : 1e-6);
-        v[q] += ep + lam * (a.droid ? v[q] : hd[q]);
-      }
+      if (r < bw && c == r) v[q] = damped_diag(a, c0 + r, 6 * n_free, v[q], hd[q]);
       Ls[r][c] = v[q];
     }
   }
@@ -531,10 +512,8 @@ __global__ __launch_bounds__(256) void chol_syrk_kernel(BAArgs a, int k) {
   if (!chol_active(a, n)) return;
   const int c0 = CT * k;
   if (c0 >= n) return;
-  int ti = (int)((sqrtf(8.0f * (float)blockIdx.x + 1.0f) - 1.0f) * 0.5f);
-  while ((ti + 1) * (ti + 2) / 2 <= (int)blockIdx.x) ++ti;
-  while (ti * (ti + 1) / 2 > (int)blockIdx.x) --ti;
-  const int tj = blockIdx.x - ti * (ti + 1) / 2;
+  int ti, tj;
+  tri_index((int)blockIdx.x, ti, tj);
   const int Ri = CT * (k + 1 + ti), Rj = CT * (k + 1 + tj);
   if (Ri > n || Rj >= n) return;  // row tile must hold a row <= n, column tile a column < n
   const BAWs& w = a.w;
@@ -643,11 +622,7 @@ __global__ __launch_bounds__(512) void chol_backsub_kernel(BAArgs a) {
   }
   const bool bad = w.info[7] != 0;
   if (t == 0 && bad) w.info[2] += 1;
-  for (int dd = t; dd < n; dd += 512) {
-    double x = ys[dd];
-    if (bad || !(x == x)) x = 0.0;  // zero step on a failed factorisation
-    w.dx[dd] = (float)x;
-  }
+  for (int dd = t; dd < n; dd += 512) store_step(w, dd, ys[dd], bad);
   __syncthreads();
   apply_retraction(a, t, 512, n_free);
 }
