@@ -292,6 +292,34 @@ int vipe_dense_ba(const vipe_ba_params* p, float* d_poses, float* d_disps, const
                   const int64_t* d_qj, const int64_t* d_di, void* d_workspace, int64_t workspace_bytes,
                   int* d_info, void* stream);
 
+/* Marginal covariances of the damped, weighted linear system ONE Gauss-Newton iteration of vipe_dense_ba would solve at
+ * the given state: H = [[B, E], [E^T, C]] with C diagonal (per-pixel disparities), S = B - E C^-1 E^T.  The network's
+ * confidence weights act as inverse variances; there is no noise scale.  Two calls, with the caller's inverse of S between
+ * them (an n x n factorisation, n <= 6 n_poses + tail; the library does not invert):
+ *
+ * vipe_dense_ba_linearize: the plan, the sensor-prior test and the accumulate kernels of one iteration (reuse_plan,
+ *   path_hint and solver_options as in vipe_dense_ba; n_iters is ignored), no solve, no retraction: poses / disps /
+ *   intrinsics / rig are only read.  d_S_out [>= n, ld_out] fp64, ld_out >= 6 n_poses + tail: the symmetric reduced system
+ *   WITH the Levenberg-Marquardt damping of the pose / intrinsics / rig rows, n = d_info[3] rows and columns written.
+ *   The workspace then holds the per-pixel blocks the marginals read; nothing else may run in it before
+ *   vipe_dense_ba_marginals has.
+ * vipe_dense_ba_marginals: p and d_workspace of that linearize call, d_Sinv [n, ld] fp64 = S^-1, full symmetric
+ *   (NULL with ld = 0 when n = 0).
+ *   d_disp_var [n_poses*V, ht*wd] f32: var = 1/C + (e^T S^-1 e)/C^2 for every pixel of a FREE disparity frame (e: the
+ *   pixel's column of E); d_pose_cov [n_poses, 6, 6] fp64: the diagonal block of S^-1 of every FREE pose, in the solver's
+ *   left tangent (X <- Exp(dx) X), order (translation, rotation) of dx.  Rows of frames / poses that are not free in this
+ *   problem (fixed, motion_only, limited_disp, without terms) are NOT written: prefill with NaN.  Either output may be
+ *   NULL.  On return S and Hd of the workspace are zero again, as a vipe_dense_ba call leaves them, so a later call with
+ *   reuse_plan in this workspace stays valid.  Plain stores in a fixed summation order: repeated calls are bitwise equal.
+ * Live semantics only (the DROID-signature vipe_ba is not covered). */
+int vipe_dense_ba_linearize(const vipe_ba_params* p, const float* d_poses, const float* d_disps, const float* d_disps_sens,
+                            const float* d_intrinsics, const float* d_rig, const float* d_target, const float* d_weight,
+                            const float* d_disp_damping, const int64_t* d_pi, const int64_t* d_qi, const int64_t* d_pj,
+                            const int64_t* d_qj, const int64_t* d_di, void* d_workspace, int64_t workspace_bytes,
+                            double* d_S_out, int ld_out, int* d_info, void* stream);
+int vipe_dense_ba_marginals(const vipe_ba_params* p, void* d_workspace, const double* d_Sinv, int ld, float* d_disp_var,
+                            double* d_pose_cov, void* stream);
+
 /* slam_ext.ba with the DROID signature (slam.cpp:31, geom_kernels.cu:1273-1404; dormant in the reference):
  * single pinhole intrinsics[4] at 1/8 scale, targets/weights [E,2,ht,wd], eta [t1-t0... see file], poses/disps
  * updated in place; dx [t1-t0,6], dz [K,ht*wd] written for the last iteration. */

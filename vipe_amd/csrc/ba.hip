@@ -32,7 +32,9 @@
 //                        two-chain bodies that call it, ba_solve_band_kernel
 //   ba_solve_dense.inc   ba_solve_dense_kernel
 //   ba_solve_global.inc  ba_solve_kernel + the tiled Cholesky     ba_retract.inc       ba_retract_kernel, clamp_min_kernel
-// This file keeps the overlap protocol, run_iters and the exported entry points.
+//   ba_marginals.inc     ba_term_slot_kernel, ba_export_reduced_kernel, ba_disp_variance_kernel, ba_marginals_finish_kernel:
+//                        marginal covariances from the blocks one linearisation leaves in the workspace
+// This file keeps the overlap protocol, launch_accumulate, run_iters and the exported entry points.
 //
 // Comments of the form `// @stamp N`, `// @stampk N`, `// @wstampk N`, `// @bstamp N`, `// @bwave N`, `// @astamp N`,
 // `// @kstamp N` / `// @kstampc N` in the parts mark phase boundaries: scratch/make_ba_stamps.py expands the includes and
@@ -51,6 +53,7 @@ namespace {
 #include "ba_solve_dense.inc"
 #include "ba_solve_global.inc"
 #include "ba_retract.inc"
+#include "ba_marginals.inc"
 
 // Event `after the accumulate kernels of this iteration` on the BA stream; see overlap_piece
 hipEvent_t overlap_event() {
@@ -74,6 +77,33 @@ int overlap_piece(const vipe_ba_params& p, hipEvent_t ev, int piece, int n_piece
   return p.overlap_fn(p.overlap_user, piece, n_pieces, p.overlap_stream);
 }
 
+// the accumulate kernels of one linearisation (path_hint: what the caller learnt from an earlier call with this plan; 0
+// launches both paths and the inapplicable one exits at once)
+template <int CAM, int F>
+void launch_accumulate(const BAArgs& a, hipStream_t s) {
+  const int tiles = (a.P + TILE - 1) / TILE;
+  static std::atomic<uint64_t> tmpl_set{0};  // one per <CAM, F> instantiation of this function
+  vipe_once_per_device(tmpl_set, [] {
+    (void)hipFuncSetAttribute((const void*)ba_accum_mfma_kernel<CAM, F>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)accum_mfma_lds());
+    (void)hipFuncSetAttribute((const void*)ba_walk_kernel<CAM, F>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)walk_lds());
+    (void)hipFuncSetAttribute((const void*)ba_walk_rig_kernel<CAM, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)walk_rig_lds());
+    (void)hipFuncSetAttribute((const void*)ba_walk_rig_kernel<CAM, RG_VMAX>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)walk_rig_lds());
+  });
+  if (a.mv) {
+    // multi-view rigs: local-block walk, Schur Gram over the stacked E rows
+    if (a.p.n_views <= 4) ba_walk_rig_kernel<CAM, 4><<<dim3(tiles, a.nF), TILE, walk_rig_lds(), s>>>(a);
+    else ba_walk_rig_kernel<CAM, RG_VMAX><<<dim3(tiles, a.nF), TILE, walk_rig_lds(), s>>>(a);
+    ba_schur_kernel<0><<<dim3(SC_GRID, a.nF), TILE, 0, s>>>(a);
+    return;
+  }
+  const int hint = a.force_general ? 0 : a.p.path_hint;
+  if (!(hint & 2)) ba_accum_mfma_kernel<CAM, F><<<dim3(tiles, a.nF), TILE, accum_mfma_lds(), s>>>(a);
+  if (!(hint & 1)) {
+    ba_walk_kernel<CAM, F><<<dim3(tiles, a.nF), TILE, walk_lds(), s>>>(a);
+    ba_schur_kernel<F><<<dim3(SC_GRID, a.nF), TILE, 0, s>>>(a);
+  }
+}
+
 template <int CAM, int F>
 int run_iters(const BAArgs& a, hipStream_t s, int* pieces_done) {
   const int tiles = (a.P + TILE - 1) / TILE;
@@ -92,13 +122,6 @@ int run_iters(const BAArgs& a, hipStream_t s, int* pieces_done) {
     (void)hipFuncSetAttribute((const void*)ba_solve_dense_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     (void)hipFuncSetAttribute((const void*)chol_backsub_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024);
   });
-  static std::atomic<uint64_t> tmpl_set{0};  // one per <CAM, F> instantiation of this function
-  vipe_once_per_device(tmpl_set, [] {
-    (void)hipFuncSetAttribute((const void*)ba_accum_mfma_kernel<CAM, F>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)accum_mfma_lds());
-    (void)hipFuncSetAttribute((const void*)ba_walk_kernel<CAM, F>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)walk_lds());
-    (void)hipFuncSetAttribute((const void*)ba_walk_rig_kernel<CAM, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)walk_rig_lds());
-    (void)hipFuncSetAttribute((const void*)ba_walk_rig_kernel<CAM, RG_VMAX>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)walk_rig_lds());
-  });
   // S / Hd start each accumulation zeroed: by ba_retract_kernel of the previous iteration when it runs (not motion_only),
   // also across calls when the caller vouches for the workspace (reuse_plan: same key, hence the same motion_only), else
   // by memsets
@@ -112,10 +135,8 @@ int run_iters(const BAArgs& a, hipStream_t s, int* pieces_done) {
       if (e1 != hipSuccess || e2 != hipSuccess) return (int)(e1 != hipSuccess ? e1 : e2);
     }
     if (a.mv) {
-      // multi-view rigs: local-block walk, Schur Gram over the stacked E rows, global-memory Cholesky with the dense tail
-      if (a.p.n_views <= 4) ba_walk_rig_kernel<CAM, 4><<<dim3(tiles, a.nF), TILE, walk_rig_lds(), s>>>(a);
-      else ba_walk_rig_kernel<CAM, RG_VMAX><<<dim3(tiles, a.nF), TILE, walk_rig_lds(), s>>>(a);
-      ba_schur_kernel<0><<<dim3(SC_GRID, a.nF), TILE, 0, s>>>(a);
+      // multi-view rigs: global-memory Cholesky with the dense tail
+      launch_accumulate<CAM, F>(a, s);
       if (ev && hipEventRecord(ev, s) != hipSuccess) return VIPE_EINVAL;
       ba_solve_kernel<<<1, SOLVE_T, solve_lds, s>>>(a, panel_cap);
       launch_tiled_cholesky(a, s);
@@ -132,11 +153,7 @@ int run_iters(const BAArgs& a, hipStream_t s, int* pieces_done) {
     const bool prof = a.p.profile_ev0 && a.p.profile_ev1 &&
                       it == (a.p.profile_iter < 0 || a.p.profile_iter >= a.p.n_iters ? a.p.n_iters - 1 : a.p.profile_iter);
     if (prof && hipEventRecord((hipEvent_t)a.p.profile_ev0, s) != hipSuccess) return VIPE_EINVAL;
-    if (!(hint & 2)) ba_accum_mfma_kernel<CAM, F><<<dim3(tiles, a.nF), TILE, accum_mfma_lds(), s>>>(a);
-    if (!(hint & 1)) {
-      ba_walk_kernel<CAM, F><<<dim3(tiles, a.nF), TILE, walk_lds(), s>>>(a);
-      ba_schur_kernel<F><<<dim3(SC_GRID, a.nF), TILE, 0, s>>>(a);
-    }
+    launch_accumulate<CAM, F>(a, s);
     if (prof && hipEventRecord((hipEvent_t)a.p.profile_ev1, s) != hipSuccess) return VIPE_EINVAL;
     if (ev && hipEventRecord(ev, s) != hipSuccess) return VIPE_EINVAL;
     if (!(hint & 8)) ba_solve_band_kernel<<<1, 2 * BAND_T, band_lds, s>>>(a, (int)(band_lds / sizeof(double)));
@@ -153,6 +170,23 @@ int run_iters(const BAArgs& a, hipStream_t s, int* pieces_done) {
     if (!a.p.motion_only) ba_retract_kernel<F><<<dim3(tiles, a.nF), TILE, 0, s>>>(a);
   }
   return vipe_launch_status();
+}
+
+// what the live entry points derive from the parameters alone (array pointers and the workspace are the caller's to fill)
+BAArgs live_args(const vipe_ba_params& p) {
+  BAArgs a = {};
+  a.p = p;
+  a.P = p.ht * p.wd;
+  a.nF = p.n_poses * p.n_views;
+  a.D = p.camera == VIPE_CAM_MEI ? 1 : 0;
+  a.mv = is_multiview(p) ? 1 : 0;
+  a.nintr = tail_intr(p);
+  a.ntail = a.nintr + tail_rig(p);
+  a.force_general = (p.solver_options & VIPE_BA_OPT_GENERAL_ACCUMULATE) != 0;
+  a.band2 = !(p.solver_options & VIPE_BA_OPT_ONE_CHAIN);
+  a.droid = 0;
+  a.dz_out = nullptr;
+  return a;
 }
 
 }  // namespace
@@ -174,22 +208,11 @@ VIPE_EXPORT int vipe_dense_ba(const vipe_ba_params* p, float* d_poses, float* d_
   VIPE_CHECK_ARG(p->M == 0 || (d_target && d_weight && d_pi && d_qi && d_pj && d_qj && d_di));
   if (is_multiview(*p) && p->n_views > RG_VMAX) return VIPE_EUNSUPPORTED;  // rigs of up to 8 cameras
   if ((int64_t)p->n_poses * p->n_views > 65535) return VIPE_EINVAL;
-  BAArgs a;
-  a.p = *p;
+  BAArgs a = live_args(*p);
   if ((int64_t)carve(*p, (char*)d_workspace, &a.w) > workspace_bytes) return VIPE_ENOSPACE;
   a.poses = d_poses; a.disps = d_disps; a.intr = d_intrinsics; a.rig = d_rig;
   a.sens = d_disps_sens; a.target = d_target; a.weight = d_weight; a.eta = d_disp_damping;
   a.pi = d_pi; a.qi = d_qi; a.pj = d_pj; a.qj = d_qj; a.di = d_di;
-  a.P = p->ht * p->wd;
-  a.nF = p->n_poses * p->n_views;
-  a.D = p->camera == VIPE_CAM_MEI ? 1 : 0;
-  a.mv = is_multiview(*p) ? 1 : 0;
-  a.nintr = tail_intr(*p);
-  a.ntail = a.nintr + tail_rig(*p);
-  a.force_general = (p->solver_options & VIPE_BA_OPT_GENERAL_ACCUMULATE) != 0;
-  a.band2 = !(p->solver_options & VIPE_BA_OPT_ONE_CHAIN);
-  a.droid = 0;
-  a.dz_out = nullptr;
   hipStream_t s = as_stream(stream);
   int rc = VIPE_OK, pieces_done = 0;
   if (p->M > 0 && p->n_iters > 0) {
@@ -215,6 +238,74 @@ VIPE_EXPORT int vipe_dense_ba(const vipe_ba_params* p, float* d_poses, float* d_
   // buffer.py:525: disps.clamp_(min=1e-3) over the whole buffer handed in
   const int64_t nd = (int64_t)a.nF * a.P;
   clamp_min_kernel<<<(int)std::min<int64_t>((nd + 255) / 256, 2048), 256, 0, s>>>(d_disps, nd, 1e-3f);
+  return vipe_launch_status();
+}
+
+// ---- marginal covariances of the live dense BA (ba_marginals.inc).  Two calls with the caller's inverse of the reduced
+// system in between: linearize leaves C / E_kk / E_j / E_f / E_t and the undamped S, Hd in the workspace and hands out the
+// damped symmetric S; marginals reads them with S^-1 and zeroes S / Hd again.
+VIPE_EXPORT int vipe_dense_ba_linearize(const vipe_ba_params* p, const float* d_poses, const float* d_disps,
+                                        const float* d_disps_sens, const float* d_intrinsics, const float* d_rig,
+                                        const float* d_target, const float* d_weight, const float* d_disp_damping,
+                                        const int64_t* d_pi, const int64_t* d_qi, const int64_t* d_pj, const int64_t* d_qj,
+                                        const int64_t* d_di, void* d_workspace, int64_t workspace_bytes, double* d_S_out,
+                                        int ld_out, int* d_info, void* stream) {
+  VIPE_CHECK_ARG(p && d_poses && d_disps && d_disps_sens && d_intrinsics && d_rig && d_disp_damping && d_workspace && d_S_out);
+  VIPE_CHECK_ARG(p->n_poses > 0 && p->n_views > 0 && p->ht > 0 && p->wd > 0 && p->M >= 0);
+  VIPE_CHECK_ARG(p->t0 <= p->t1 && p->intr_factor > 0);
+  VIPE_CHECK_ARG(p->camera == VIPE_CAM_PINHOLE || p->camera == VIPE_CAM_MEI);
+  VIPE_CHECK_ARG(p->M == 0 || (d_target && d_weight && d_pi && d_qi && d_pj && d_qj && d_di));
+  if (is_multiview(*p) && p->n_views > RG_VMAX) return VIPE_EUNSUPPORTED;
+  if ((int64_t)p->n_poses * p->n_views > 65535) return VIPE_EINVAL;
+  BAArgs a = live_args(*p);
+  if ((int64_t)carve(*p, (char*)d_workspace, &a.w) > workspace_bytes) return VIPE_ENOSPACE;
+  VIPE_CHECK_ARG(ld_out >= 6 * p->n_poses + a.ntail);  // the bound carve sizes S by; n = info[3] rows are written
+  // the kernels are shared with the solver and take the state as mutable; nothing launched here writes it
+  a.poses = const_cast<float*>(d_poses); a.disps = const_cast<float*>(d_disps);
+  a.intr = const_cast<float*>(d_intrinsics); a.rig = const_cast<float*>(d_rig);
+  a.sens = d_disps_sens; a.target = d_target; a.weight = d_weight; a.eta = d_disp_damping;
+  a.pi = d_pi; a.qi = d_qi; a.pj = d_pj; a.qj = d_qj; a.di = d_di;
+  hipStream_t s = as_stream(stream);
+  ba_sens_kernel<<<a.nF, 256, 0, s>>>(d_disps_sens, a.w.sens_sum, a.P, a.w.info);
+  if (!(p->reuse_plan && p->M > 0)) ba_plan_kernel<<<1, 1024, 0, s>>>(a);
+  if (!(p->reuse_plan && !p->motion_only && p->M > 0)) {  // as run_iters: a vouched-for workspace holds S = Hd = 0
+    hipError_t e1 = hipMemsetAsync(a.w.S, 0, sizeof(double) * (size_t)a.w.ld * a.w.ld, s);
+    hipError_t e2 = hipMemsetAsync(a.w.Hd, 0, sizeof(double) * ((size_t)a.w.ld - 1), s);
+    if (e1 != hipSuccess || e2 != hipSuccess) return (int)(e1 != hipSuccess ? e1 : e2);
+  }
+  if (p->M > 0) {
+    ba_term_slot_kernel<<<(p->M + 255) / 256, 256, 0, s>>>(a);
+    const int F = p->optimize_intrinsics ? 1 + a.D : 0;
+    if (p->camera == VIPE_CAM_PINHOLE) F ? launch_accumulate<VIPE_CAM_PINHOLE, 1>(a, s) : launch_accumulate<VIPE_CAM_PINHOLE, 0>(a, s);
+    else F ? launch_accumulate<VIPE_CAM_MEI, 2>(a, s) : launch_accumulate<VIPE_CAM_MEI, 0>(a, s);
+  }
+  const int64_t nn = (int64_t)(a.w.ld - 1) * (a.w.ld - 1);
+  ba_export_reduced_kernel<<<(int)std::min<int64_t>((nn + 255) / 256, 2048), 256, 0, s>>>(a, d_S_out, ld_out);
+  if (d_info) {
+    hipError_t e = hipMemcpyAsync(d_info, a.w.info, 8 * sizeof(int), hipMemcpyDeviceToDevice, s);
+    if (e != hipSuccess) return (int)e;
+  }
+  return vipe_launch_status();
+}
+
+VIPE_EXPORT int vipe_dense_ba_marginals(const vipe_ba_params* p, void* d_workspace, const double* d_Sinv, int ld,
+                                        float* d_disp_var, double* d_pose_cov, void* stream) {
+  VIPE_CHECK_ARG(p && d_workspace);
+  VIPE_CHECK_ARG(p->n_poses > 0 && p->n_views > 0 && p->ht > 0 && p->wd > 0 && p->M >= 0 && ld >= 0);
+  VIPE_CHECK_ARG(p->camera == VIPE_CAM_PINHOLE || p->camera == VIPE_CAM_MEI);
+  if (is_multiview(*p) && p->n_views > RG_VMAX) return VIPE_EUNSUPPORTED;
+  if ((int64_t)p->n_poses * p->n_views > 65535) return VIPE_EINVAL;
+  BAArgs a = live_args(*p);
+  carve(*p, (char*)d_workspace, &a.w);
+  hipStream_t s = as_stream(stream);
+  const int tiles = (a.P + TILE - 1) / TILE;
+  // no free disparity without terms or under motion_only; no unknowns (ld == 0): the caller has no inverse to hand in
+  if (p->M > 0 && !p->motion_only && d_disp_var) {
+    VIPE_CHECK_ARG(d_Sinv || ld == 0);
+    ba_disp_variance_kernel<<<dim3(tiles, a.nF), TILE, 0, s>>>(a, d_Sinv, ld, d_disp_var);
+  }
+  const int64_t ns = (int64_t)a.w.ld * a.w.ld;
+  ba_marginals_finish_kernel<<<(int)std::min<int64_t>((ns + 255) / 256, 2048), 256, 0, s>>>(a, ld > 0 ? d_Sinv : nullptr, ld, d_pose_cov);
   return vipe_launch_status();
 }
 

@@ -26,6 +26,7 @@ struct BAWs {
   float* dx;        // [nmax]
   double* Wi;       // [ceil(nmax / 64)][64][64] inverses of the diagonal factor tiles (tiled Cholesky)
   int* krow;        // [nF] DROID mode: row of frame k in the sorted unique set arange(t0,t1) U ii (eta / dz row)
+  int* mslot;       // [M] marginals: slot of the target pose of the term at each CSR position, or -1 (ba_term_slot_kernel)
   int ld;           // nmax + 1
 };
 
@@ -90,6 +91,7 @@ size_t carve(const vipe_ba_params& p, char* base, BAWs* out) {
   w.dx = (float*)take(4 * nmax);
   w.Wi = (double*)take(8 * 64 * 64 * ((nmax + 63) / 64));
   w.krow = (int*)take(4 * (nF + 1));
+  w.mslot = (int*)take(4 * (M + 1));
   w.ld = (int)(nmax + 1);
   if (out) *out = w;
   return off;

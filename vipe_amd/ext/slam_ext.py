@@ -131,24 +131,8 @@ def dense_ba(poses, disps, disps_sens, intrinsics, rig, target, weight, disp_dam
     L = lib()
     nbytes = L.vipe_dense_ba_workspace_bytes(ctypes.byref(p))
     require(nbytes > 0, "bad BA parameters")
-    key = None
-    if state is None:
-        ws = _workspace(poses.device, nbytes)
-    else:
-        # `state`: a dict owned by ONE caller (a FactorGraph) holding a private workspace.  When that caller vouches, through
-        # `plan_key`, that the index arrays are the ones of its previous call, the plan left in the workspace is reused
-        # (vipe_ba_params.reuse_plan); everything else that shapes the plan is part of the key checked here.
-        ws = state.get("ws")
-        if ws is None or ws.numel() < nbytes or ws.device != poses.device:
-            ws = torch.empty(int(nbytes * 1.25) + 1024, dtype=torch.uint8, device=poses.device)
-            state["ws"], state["key"] = ws, None
-        key = None if plan_key is None else (plan_key, ws.data_ptr(), n_poses, V, ht, wd, M, int(t0), int(t1), int(motion_only),
-                                             int(limited_disp), int(optimize_intrinsics), int(optimize_rig_rotation), camera,
-                                             tuple(int(x.data_ptr()) for x in (pi, qi, pj, qj, di)))
-        p.reuse_plan = int(key is not None and state.get("key") == key and PLAN_REUSE)
-        # a call that launches nothing (no terms / no iterations) leaves the workspace as it found it: it vouches for nothing
-        state["key"] = key if (M > 0 and int(n_iters) > 0) else None
-        p.path_hint = _path_hint(state, key)
+    ws, key = _plan_workspace(p, nbytes, state, plan_key, camera, (pi, qi, pj, qj, di), poses.device,
+                              launches=M > 0 and int(n_iters) > 0)
     learn = state is not None and key is not None and p.path_hint == 0 and "pending" not in state and M > 0 and n_iters > 0 \
         and not torch.cuda.is_current_stream_capturing() and PLAN_REUSE
     info = torch.zeros(8, dtype=torch.int32, device=poses.device) if (want_info or learn) else None
@@ -162,6 +146,106 @@ def dense_ba(poses, disps, disps_sens, intrinsics, rig, target, weight, disp_dam
         ev.record()
         state["pending"] = (key, host, ev)
     return info
+
+
+def _plan_workspace(p, nbytes, state, plan_key, camera, index_arrays, device, launches):
+    """-> (workspace, plan key or None); sets p.reuse_plan / p.path_hint.  `state` None: the shared grow-only workspace.
+    Else `state` is a dict owned by ONE caller (a FactorGraph) holding a private workspace.  When that caller vouches, through
+    `plan_key`, that the index arrays are the ones of its previous call, the plan left in the workspace is reused
+    (vipe_ba_params.reuse_plan); everything else that shapes the plan is part of the key checked here."""
+    if state is None:
+        return _workspace(device, nbytes), None
+    ws = state.get("ws")
+    if ws is None or ws.numel() < nbytes or ws.device != device:
+        ws = torch.empty(int(nbytes * 1.25) + 1024, dtype=torch.uint8, device=device)
+        state["ws"], state["key"] = ws, None
+    key = None if plan_key is None else (plan_key, ws.data_ptr(), p.n_poses, p.n_views, p.ht, p.wd, p.M, p.t0, p.t1, p.motion_only,
+                                         p.limited_disp, p.optimize_intrinsics, p.optimize_rig_rotation, camera,
+                                         tuple(int(x.data_ptr()) for x in index_arrays))
+    p.reuse_plan = int(key is not None and state.get("key") == key and PLAN_REUSE)
+    # a call that launches nothing (no terms / no iterations) leaves the workspace as it found it: it vouches for nothing
+    state["key"] = key if launches else None
+    p.path_hint = _path_hint(state, key)
+    return ws, key
+
+
+def dense_ba_linearize(poses, disps, disps_sens, intrinsics, rig, target, weight, disp_damping, pi, qi, pj, qj, di, t0, t1,
+                       pose_damping, pose_ep, motion_only=False, limited_disp=False, optimize_intrinsics=False,
+                       optimize_rig_rotation=False, camera="pinhole", alpha=0.001, n_poses=None, state=None, plan_key=None,
+                       solver_options=0):
+    """First half of `dense_ba_marginals` (`vipe_dense_ba_linearize`): the normal equations of ONE Gauss-Newton iteration
+    at the given state, which is only read.  -> (S, info, ctx): the damped symmetric reduced system [n,n] float64
+    (n = info[3]; reading it back synchronises the stream once), the plan's facts, and what `dense_ba_marginals_apply`
+    needs.  Nothing else may run in the workspace between the two halves."""
+    check_gpu_contig(poses, disps, disps_sens, intrinsics, rig, target, weight, disp_damping, pi, qi, pj, qj, di)
+    for t in (poses, disps, disps_sens, intrinsics, rig, target, weight, disp_damping):
+        require(t.dtype == torch.float32, "dense_ba_marginals works in float32 (the reference's BA dtype)")
+    V = rig.shape[0]
+    n_poses = poses.shape[0] if n_poses is None else int(n_poses)
+    require(disps.dim() == 3 and disps.shape[0] >= n_poses * V, "disps must be [n_poses*V,ht,wd]")
+    _, ht, wd = disps.shape
+    M = pi.shape[0]
+    require(target.numel() == M * ht * wd * 2 and weight.numel() == M * ht * wd * 2, "target/weight must be [M,P,2]")
+    p = BAParams(n_poses=n_poses, n_views=V, ht=ht, wd=wd, M=M, t0=int(t0), t1=int(t1), n_iters=1,
+                 pose_damping=float(pose_damping), pose_ep=float(pose_ep), motion_only=int(motion_only),
+                 limited_disp=int(limited_disp), optimize_intrinsics=int(optimize_intrinsics),
+                 optimize_rig_rotation=int(optimize_rig_rotation), camera=CAMERA_CODE[camera], alpha=float(alpha),
+                 weight_scale=0.001, intr_factor=8.0, reuse_plan=0, path_hint=0, solver_options=int(solver_options))
+    L = lib()
+    nbytes = L.vipe_dense_ba_workspace_bytes(ctypes.byref(p))
+    check(min(nbytes, 0), "dense_ba_linearize")
+    ws, _ = _plan_workspace(p, nbytes, state, plan_key, camera, (pi, qi, pj, qj, di), poses.device, launches=M > 0)
+    D = intrinsics.shape[1] - 4
+    nmax = 6 * n_poses + (V * (1 + D) + 6 * (V - 1) if V > 1 else 1 + D)  # the bound the workspace sizes S by
+    S = torch.empty((nmax, nmax), dtype=torch.float64, device=poses.device)
+    info = torch.zeros(8, dtype=torch.int32, device=poses.device)
+    check(L.vipe_dense_ba_linearize(ctypes.byref(p), ptr(poses), ptr(disps), ptr(disps_sens), ptr(intrinsics), ptr(rig),
+                                    ptr(target), ptr(weight), ptr(disp_damping), ptr(_i64(pi)), ptr(_i64(qi)),
+                                    ptr(_i64(pj)), ptr(_i64(qj)), ptr(_i64(di)), ptr(ws), ws.numel(), ptr(S), nmax,
+                                    ptr(info), stream_ptr(poses)), "dense_ba_linearize")
+    n = int(info[3].item())
+    return S[:n, :n], info, (p, ws, (n_poses, V, ht, wd))
+
+
+def invert_reduced_system(S):
+    """S^-1 of the damped reduced system, float64 on the device: one n x n Cholesky factorisation (n <= ~1500) and
+    cholesky_inverse - plumbing between the two library calls, not a hot path."""
+    return torch.cholesky_inverse(torch.linalg.cholesky(S)).contiguous()
+
+
+def dense_ba_marginals_apply(ctx, Sinv):
+    """Second half (`vipe_dense_ba_marginals`): -> (disp_var [n_poses*V,ht,wd] float32, pose_cov [n_poses,6,6] float64),
+    NaN where the frame / pose is not free.  Plain stores in a fixed order: the same `ctx` and `Sinv` give the same bits."""
+    p, ws, (n_poses, V, ht, wd) = ctx
+    n = 0 if Sinv is None else int(Sinv.shape[0])
+    if n:
+        require(Sinv.is_cuda and Sinv.dtype == torch.float64 and Sinv.is_contiguous() and Sinv.shape == (n, n), "Sinv: [n,n] float64")
+    disp_var = torch.full((n_poses * V, ht, wd), float("nan"), dtype=torch.float32, device=ws.device)
+    pose_cov = torch.full((n_poses, 6, 6), float("nan"), dtype=torch.float64, device=ws.device)
+    check(lib().vipe_dense_ba_marginals(ctypes.byref(p), ptr(ws), ptr(Sinv) if n else None, n, ptr(disp_var), ptr(pose_cov),
+                                        stream_ptr(ws)), "dense_ba_marginals")
+    return disp_var, pose_cov
+
+
+def dense_ba_marginals(*args, **kwargs):
+    """Marginal covariances of the linear system ONE Gauss-Newton iteration of `dense_ba` would solve at the given state
+    (same arguments, minus iterations and overlap; nothing is modified) -> (disp_var, pose_cov, info).
+
+    disp_var [n_poses*V,ht,wd] float32: variance of every pixel of a free disparity frame, 1/C + e^T S^-1 e / C^2.
+    pose_cov [n_poses,6,6] float64: covariance of every free pose in the solver's left tangent (X <- Exp(dx) X), in the
+    order of dx (translation, rotation).  Rows that are not free in this problem (fixed poses, frames without terms,
+    everything under `motion_only`, `limited_disp`) are NaN.  info: as `dense_ba(want_info=True)`.
+
+    These are the covariances of the DAMPED, WEIGHTED problem: the network's confidence weights act as inverse variances
+    (with the 0.001 weight scale), the disparity damping and the Levenberg-Marquardt damping of the pose rows are part of
+    the system, and there is no noise scale - a relative measure of how well each unknown is determined.
+
+    Runs in the shared workspace unless the caller passes its own `state` (then the plan in it stays valid, as with
+    `dense_ba`).  The reduced system is inverted between the two library calls (`invert_reduced_system`)."""
+    S, info, ctx = dense_ba_linearize(*args, **kwargs)
+    Sinv = invert_reduced_system(S) if S.shape[0] else None
+    disp_var, pose_cov = dense_ba_marginals_apply(ctx, Sinv)
+    return disp_var, pose_cov, info
 
 
 def _path_hint(state, key):

@@ -161,6 +161,34 @@ class GraphBuffer:
                           plan=None, ba_state=None, plan_key=None, overlap=None):
         """buffer.py:373-525, in place on self.poses / self.disps (/ self.intrinsics).  `plan` = (pi, qi, di, pj, qj)
         of `expand_edge_multiview(ii, jj)` when the caller already holds it (the reference re-expands every call)."""
+        args, kw = self._ba_problem(target, weight, disp_damping, ii, jj, t0, t1, plan)
+        self.touch()
+        return slam_ext.dense_ba(
+            *args, n_iters, pose_damping, pose_ep, motion_only, limited_disp, optimize_intrinsics, optimize_rig_rotation,
+            **kw, want_info=verbose, state=ba_state, plan_key=plan_key, overlap=overlap)
+
+    def ba_marginals(self, target, weight, disp_damping, ii, jj, t0, t1, pose_damping, pose_ep, motion_only, limited_disp,
+                     optimize_intrinsics, optimize_rig_rotation, plan=None):
+        """Marginal covariances of the linear system ONE Gauss-Newton iteration of `bundle_adjustment` with these
+        arguments would solve at the buffer's current state (`slam_ext.dense_ba_marginals`; the same `plan` / base offset /
+        sparse-track fold); nothing is modified.  -> (disp_var [n*V,h,w] f32, pose_cov [n,6,6] f64, info) with
+        n = max(n_frames, t1), rows by buffer slot: NaN where the frame / pose is not free in this problem (fixed poses such
+        as the gauge keyframe, frames without terms, everything under motion_only).  Covariances of the DAMPED, WEIGHTED
+        problem: the network's confidence weights act as inverse variances, there is no noise scale; pose blocks in the
+        solver's left tangent (X <- Exp(dx) X), in the order of dx."""
+        args, kw = self._ba_problem(target, weight, disp_damping, ii, jj, t0, t1, plan)
+        disp_var, pose_cov, info = slam_ext.dense_ba_marginals(
+            *args, pose_damping, pose_ep, motion_only, limited_disp, optimize_intrinsics, optimize_rig_rotation, **kw)
+        base = self.poses.shape[0] - args[0].shape[0]
+        if base:  # the library saw the buffer rows from `base` on
+            nan = float("nan")
+            disp_var = torch.cat([disp_var.new_full((base * self.n_views,) + tuple(disp_var.shape[1:]), nan), disp_var])
+            pose_cov = torch.cat([pose_cov.new_full((base, 6, 6), nan), pose_cov])
+        return disp_var, pose_cov, info
+
+    def _ba_problem(self, target, weight, disp_damping, ii, jj, t0, t1, plan):
+        """-> (positional arguments of `slam_ext.dense_ba` up to t1, keyword arguments) of the BA problem over the
+        buffer: the expansion of the edges (or the caller's `plan`), rows from `base` on, the sparse-track term folded in"""
         assert t0 <= t1
         base = 0
         if plan is not None and len(plan) == 6:
@@ -181,14 +209,10 @@ class GraphBuffer:
                 target_frame_inds=self.tstamp[pj + base], image_size=(self.height, self.width),
                 dense_disp_size=(self.height // 8, self.width // 8))
             target, weight = fold_flow_terms(target, weight, s_target.flatten(1, 2), s_weight.flatten(1, 2))
-        self.touch()
-        return slam_ext.dense_ba(
-            self.poses[base:], self.flattened_disps[base * V:], self.flattened_disps_sens[base * V:], self.intrinsics,
-            self.rig, target.contiguous(), weight.contiguous(), disp_damping[base * V:].contiguous(), pi, qi, pj, qj, di,
-            max(int(t0) - base, 0), max(int(t1) - base, 0), n_iters,
-            pose_damping, pose_ep, motion_only, limited_disp, optimize_intrinsics, optimize_rig_rotation,
-            camera=self.camera_type, alpha=self.ba_config.dense_disp_alpha, n_poses=n_poses, want_info=verbose,
-            state=ba_state, plan_key=plan_key, overlap=overlap)
+        return ((self.poses[base:], self.flattened_disps[base * V:], self.flattened_disps_sens[base * V:], self.intrinsics,
+                 self.rig, target.contiguous(), weight.contiguous(), disp_damping[base * V:].contiguous(), pi, qi, pj, qj, di,
+                 max(int(t0) - base, 0), max(int(t1) - base, 0)),
+                dict(camera=self.camera_type, alpha=self.ba_config.dense_disp_alpha, n_poses=n_poses))
 
     def reproject_dense_disp(self, ii, jj):
         """buffer.py:527-548 -> coords [M,ht,wd,2], valid [M,ht,wd,1]."""

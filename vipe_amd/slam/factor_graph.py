@@ -204,6 +204,7 @@ class FactorGraph:
     # full resolution with THIS iteration's mask into `buffer.disps_up` (DROID-SLAM's order; `_upsample_disps`).  Needs
     # `GraphBuffer(upsample_disps=True)`.  Off: not one launch, allocation or argument differs.
     upsample = False
+    _last_ba = None  # t0, t1, damping and flags of the last BA `update` / `update_batch` issued (`marginals`' defaults)
 
     def __init__(self, update_module, buffer, device, max_factors=48, incremental=True, cross_view=False):
         self.update_op = update_module
@@ -628,15 +629,39 @@ class FactorGraph:
             plan = P["ba_plan"]
             plan_key = (self._plan_serial, "act")
         E = target.shape[1]
-        buf.bundle_adjustment(target.view(E, -1, 2), weight.view(E, -1, 2), self.damping, ii, jj, t0,
-                              t1 if not fixed_motion else t0, itrs, 1e-3, 0.1, motion_only, limited_disp, False, False,
-                              plan=plan, ba_state=self._ba_state, plan_key=plan_key, overlap=ba_overlap)
+        self._last_ba = dict(t0=t0, t1=t1 if not fixed_motion else t0, pose_damping=1e-3, pose_ep=0.1, motion_only=motion_only,
+                             limited_disp=limited_disp, optimize_intrinsics=False, optimize_rig_rotation=False)
+        buf.bundle_adjustment(target.view(E, -1, 2), weight.view(E, -1, 2), self.damping, ii, jj, n_iters=itrs,
+                              **self._last_ba, plan=plan, ba_state=self._ba_state, plan_key=plan_key, overlap=ba_overlap)
         if self.upsample:  # after the BA: this iteration's mask on the disparities it has just produced
             self._upsample_disps(upmask, P["du"])
         if overlap:
             main.wait_stream(self._side)
             self._gate_state = gate_state
         self._index.tick()
+
+    @torch.no_grad()
+    def marginals(self, t0=None, t1=None, **flags):
+        """Marginal covariances (`GraphBuffer.ba_marginals`) of the BA problem over the graph's current edges, targets,
+        weights and damping at the buffer's current state -> (disp_var [n*V,h,w], pose_cov [n,6,6], info), rows by
+        keyframe slot, NaN where a frame / pose is not free.  Window, damping and flags default to those of the last BA
+        that `update` / `update_batch` issued (before any: `update`'s own defaults); `t0` / `t1` / `flags` override them.
+        Runs in the shared BA workspace, not in this graph's private one."""
+        P = self._edge_plan() if int(self.ii.shape[0]) else None
+        ba = dict(self._last_ba or dict(t0=P["t0"] if P else 0, t1=P["t1"] if P else 0, pose_damping=1e-3, pose_ep=0.1,
+                                        motion_only=False, limited_disp=False, optimize_intrinsics=False,
+                                        optimize_rig_rotation=False))
+        ba.update(flags)
+        ba.update({k: v for k, v in (("t0", t0), ("t1", t1)) if v is not None})
+        plan = None
+        if P is not None:
+            if "ba_plan" not in P:
+                P["ba_plan"] = self._shift_plan((P["pi"], P["qi"], P["di"], P["pj"], P["qj"]),
+                                                int(min(self._index.host["ii"].min(), self._index.host["jj"].min())))
+            plan = P["ba_plan"]
+        E = self.target.shape[1]
+        return self.buffer.ba_marginals(self.target.contiguous().view(E, -1, 2), self.weight.contiguous().view(E, -1, 2),
+                                        self.damping, self.ii, self.jj, **ba, plan=plan)
 
     @torch.no_grad()
     def update_batch(self, itrs, steps, optimize_intrinsics, optimize_rig_rotation, solver_verbose=False):
@@ -764,8 +789,9 @@ class FactorGraph:
                     self.weight[0, idx_x] = weight
                     self.damping[c["du"]] = eta
             E = self.target.shape[1]
+            self._last_ba = dict(t0=1, t1=t, pose_damping=1e-5, pose_ep=1e-2, motion_only=False, limited_disp=False,
+                                 optimize_intrinsics=optimize_intrinsics, optimize_rig_rotation=optimize_rig_rotation)
             buf.bundle_adjustment(self.target.view(E, -1, 2), self.weight.view(E, -1, 2), self.damping, self.ii, self.jj,
-                                  1, t, itrs, 1e-5, 1e-2, False, False, optimize_intrinsics, optimize_rig_rotation,
-                                  verbose=solver_verbose)
+                                  n_iters=itrs, **self._last_ba, verbose=solver_verbose)
             for upmask, du in upmasks:
                 self._upsample_disps(upmask, du)

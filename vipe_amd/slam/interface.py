@@ -73,6 +73,15 @@ class SLAMMap:
         return torch.where(torch.isinf(out), torch.zeros_like(out), out).view(H, W)
 
 
+def rescale_marginals(disp_var, pose_cov, s):
+    """The marginals of a result that is rescaled by the metric-depth factor `s` the way `FilledReturn.scale` does it
+    (disparities / s, translations * s): disparity variance / s^2; of the pose covariance [...,6,6] in the order
+    (translation, rotation) the translation block * s^2, the translation-rotation blocks * s.  -> new tensors."""
+    d = torch.ones(6, dtype=pose_cov.dtype, device=pose_cov.device)
+    d[:3] = s
+    return disp_var / (s * s), pose_cov * (d[:, None] * d[None, :])
+
+
 class SLAMOutput:
     """interface.py:143-163: what `SLAMSystem.run` returns - trajectory (camera -> world per frame, SE3 [N]), intrinsics
     [V,4], the rig, the map, the BA residual.
@@ -80,10 +89,17 @@ class SLAMOutput:
     Not in the reference, None unless `SLAMConfig.upsample_disps`: `keyframe_disps_up` [N_kf,V,H,W] f32, the keyframes'
     disparities at full SLAM resolution (the 1/8 maps through the update operator's learned convex upsampling, DROID-SLAM's
     `disps_up`), and `keyframe_disps_up_valid` [N_kf,V] bool, both aligned with `keyframe_ids`.  H x W is the resolution
-    SLAM ran at: for `run(..., native_resolution=True)` the resized and cropped size, not the native one."""
+    SLAM ran at: for `run(..., native_resolution=True)` the resized and cropped size, not the native one.
+
+    Likewise None unless `SLAMConfig.disp_uncertainty`: `keyframe_disp_var` [N_kf,V,h,w] f32 at the BA's 1/8 grid and
+    `keyframe_pose_cov` [N_kf,6,6] f64 (left tangent of the world -> camera keyframe pose, X <- Exp(dx) X, order
+    translation, rotation), aligned with `keyframe_ids`: marginal covariances of the last global BA's damped, weighted
+    linear system - the network's confidence weights act as inverse variances, without a noise scale, so they rank how
+    well pixels and poses are determined rather than give metric error bars.  NaN where not free (the gauge keyframe)."""
 
     def __init__(self, *, trajectory, intrinsics, rig=None, slam_map=None, ba_residual=0.0, keyframe_disps_up=None,
-                 keyframe_disps_up_valid=None):
+                 keyframe_disps_up_valid=None, keyframe_disp_var=None, keyframe_pose_cov=None):
+        self.keyframe_disp_var, self.keyframe_pose_cov = keyframe_disp_var, keyframe_pose_cov
         self.trajectory, self.intrinsics, self.rig, self.slam_map, self.ba_residual = trajectory, intrinsics, rig, slam_map, ba_residual
         self.keyframe_disps_up, self.keyframe_disps_up_valid = keyframe_disps_up, keyframe_disps_up_valid
 

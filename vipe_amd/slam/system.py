@@ -51,6 +51,9 @@ class SLAMConfig:
     upsample_disps: bool = False   # full-resolution keyframe disparities (`SLAMOutput.keyframe_disps_up`): the operator's
                                    # convex-upsampling mask applied after every BA of the frontend and after the last
                                    # one of every backend pass; 4 * V * H * W bytes per buffer slot.  Off: nothing changes
+    disp_uncertainty: bool = False  # marginal covariances of the last global BA (`SLAMOutput.keyframe_disp_var` /
+                                    # `keyframe_pose_cov`): one `FactorGraph.marginals` call per clip after the last backend
+                                    # pass, with that pass's BA arguments.  Off: nothing is allocated, no launch differs
     backend_lock_path: str = None        # ... and let their global-BA phases - each fills the chip by itself and wants the
                                          # pyramid budget to itself - take turns (an advisory file lock held around the two
                                          # backend passes), while the other clips' pass 1 / pass 2 run beside it
@@ -213,6 +216,8 @@ class SLAMSystem:
             self.backend.run(7)
             gb = self.backend.run(self.config.backend.backend_iters, update_depth=False)
             self.backend_edges = int(gb.host_edges()["ii"].shape[0])
+            if self.config.disp_uncertainty:  # before pass 2 appends frames behind the keyframes
+                self.marginals = gb.marginals()[:2]
             if release:
                 del gb
                 self.backend.last_graph = None
@@ -266,7 +271,13 @@ class SLAMSystem:
 
         With `SLAMConfig.upsample_disps` the output carries `keyframe_disps_up` [N_kf,V,H,W] and
         `keyframe_disps_up_valid` [N_kf,V] (aligned with `keyframe_ids`), at SLAM resolution: with native_resolution=True
-        that is the resized and cropped size (`StandardResize(...).out_size`), not the native one."""
+        that is the resized and cropped size (`StandardResize(...).out_size`), not the native one.
+
+        With `SLAMConfig.disp_uncertainty` it carries `keyframe_disp_var` [N_kf,V,h,w] (the BA's 1/8 grid) and
+        `keyframe_pose_cov` [N_kf,6,6]: marginal covariances of the last global BA's damped, weighted linear system at the
+        final keyframe state (`GraphBuffer.ba_marginals`), NaN where a frame / pose was not free (the gauge keyframe's
+        pose).  `run` applies no metric rescaling; a caller that rescales the result by a factor s (disparities / s,
+        translations * s) passes the two fields through `interface.rescale_marginals`."""
         frames = [f if isinstance(f, (list, tuple)) else [f] for f in frames]
         total, n_views = len(frames), len(frames[0])
         assert total > 0 and all(len(f) == n_views for f in frames)
@@ -306,4 +317,9 @@ class SLAMSystem:
         if b.disps_up is not None:  # slots [0, n_frames) are the keyframes again (InnerFiller.compute), in keyframe_ids' order
             up = dict(keyframe_disps_up=b.disps_up[:b.n_frames].clone(),
                       keyframe_disps_up_valid=b.disps_up_valid[:b.n_frames].clone())
+        if self.config.disp_uncertainty:  # rows by keyframe slot, i.e. in keyframe_ids' order
+            n_kf, V = self.n_keyframes, b.n_views
+            disp_var, pose_cov = self.marginals
+            up.update(keyframe_disp_var=disp_var[:n_kf * V].view(n_kf, V, *disp_var.shape[1:]).clone(),
+                      keyframe_pose_cov=pose_cov[:n_kf].clone())
         return SLAMOutput(trajectory=filled.poses.inv(), intrinsics=intrinsics, rig=SE3(b.rig.clone()), slam_map=slam_map, **up)
