@@ -738,6 +738,31 @@ def test_corr_pyramid_lookup_row_kernel_bit_exact():
     assert torch.equal(nhwc[..., :196].permute(0, 3, 1, 2), out) and torch.count_nonzero(nhwc[..., 196:]) == 0
 
 
+def test_corr_pyramid_lookup_row_kernels_ragged_group_and_channels_last():
+    """Both 8-lanes-per-pixel kernels on a source grid whose 21 pixels leave the last group of 32 ragged, target grid
+    8 x 64 (level 3 is 1 x 8, the narrowest the row kernels take): the per-level kernel in both output layouts - its
+    channels-last store and zero fill are reached with any (levels, stride) but (4, 200), which the staged kernel
+    takes - bit-exact vs the oracle, padding channels exactly zero."""
+    from vipe_amd.ext import droid_net_ext
+    rng = np.random.default_rng(22)
+    E, h1, w1, h2, w2 = 2, 3, 7, 8, 64
+    levels = [rng.normal(0, 1, (E, h1, w1, h2 >> i, w2 >> i)).astype(np.float16) for i in range(4)]
+    coords = np.stack([rng.uniform(-6, w2 + 5, (E, h1, w1)), rng.uniform(-6, h2 + 5, (E, h1, w1))], -1).astype(np.float32)
+    coords[0, 0, :7] = np.stack([np.arange(7) * 8.0, np.arange(7) * 1.0], -1)  # integer coords, the chunk phases of a row
+    coords[0, 1, 0] = (56.0, 7.0)
+    ref = {L: ocorr.corr_lookup(levels[:L], coords[None], 3)[0] for L in (3, 4)}  # [E,49 L,h1,w1]
+    assert all(0.2 < np.count_nonzero(r) / r.size < 0.6 for r in ref.values())
+    dl, dc = [T(lv) for lv in levels], T(coords)
+    out = droid_net_ext.corr_pyramid_lookup(dl, dc, 3)
+    assert np.array_equal(out.cpu().numpy().view(np.uint16), ref[4].view(np.uint16))
+    for L, stride in ((4, 200), (4, 208), (3, 152)):
+        nhwc = droid_net_ext.corr_pyramid_lookup_nhwc(dl[:L], dc, 3, stride).cpu().numpy()
+        assert nhwc.shape == (E, h1, w1, stride)
+        got = np.ascontiguousarray(nhwc[..., :49 * L].transpose(0, 3, 1, 2))
+        assert np.array_equal(got.view(np.uint16), ref[L].view(np.uint16)), (L, stride)
+        assert not nhwc[..., 49 * L:].view(np.uint16).any(), (L, stride)
+
+
 # ------------------------------------------------------------------------------------------------ factor graph (composition)
 
 

@@ -43,6 +43,7 @@
 #include <algorithm>
 
 #include "common.cuh"
+#include "corr_layout.cuh"
 
 namespace {
 
@@ -73,13 +74,11 @@ struct BuildArgs {
   int64_t n_prep;        // GEN: n; an edge with a frame outside the store is skipped (its slot is left as it was)
 };
 
-// geometry of the padded blocked layout (shared with corr_lookup.hip through include/vipe_amd.h's description)
-struct GenDims {
-  int G, S, R, nch, w2p, w3p;
+// geometry of the padded blocked layout (corr_layout.cuh) + the size of the prepared operand images of one frame
+struct GenDims : BlockedDims {
   int64_t fstride;  // halves per prepared frame
   __host__ __device__ GenDims(int h, int w)
-      : G((h * w + 63) / 64), S((w + 31) / 32), R(((h + 7) / 8) * 2), nch(S * R), w2p(8 * S), w3p((4 * S + 7) / 8 * 8),
-        fstride((int64_t)PB_C * ((int64_t)G * 64 + (int64_t)nch * 128)) {}
+      : BlockedDims(h, w), fstride((int64_t)PB_C * ((int64_t)G * 64 + (int64_t)nch * 128)) {}
 };
 
 // [n][C][h*w] -> the prepared operand images A | B of every frame (see the file header); one thread per 8 output halves
@@ -227,6 +226,8 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
       // workgroup's two instructions one 16 KiB run.  POOL: (tile sseg / 2, row pair sseg % 2) - the 2 x 8 patch whose
       // level-1 entries this thread forms (re-read from the staged tile: LDS bandwidth is not the limit here).
       const int tile = sseg >> 1, hf = sseg & 1, rg = y >> 2;
+      // dst + 8 q and d1 below must agree with BlockedDims::piece01 (corr_layout.cuh); spelled out because the run base is
+      // uniform over the workgroup here: through the per-pixel function this kernel spills registers
       half_t* dst = a.lv[0] + ((eg * nchunks + ch) * PB_M + sp1) * 128;
 #pragma unroll
       for (int s2 = 0; s2 < 2; ++s2) {
@@ -267,12 +268,14 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
           if (rg >= (a.h >> 2) || c2 >= (a.w >> 2)) l2[0] = (half_t)0;
           if (rg >= (a.h >> 2) || c2 + 1 >= (a.w >> 2)) l2[1] = (half_t)0;
           if (hf == 0) {
-            half_t* d2 = a.lv[2] + (p1g * gd.R + rg) * gd.w2p + c2;
+            const BlockedDims::Slab s2 = gd.slab23(2, es, p1_0 + sp1);
+            half_t* d2 = a.lv[2] + s2.base + rg * s2.pitch + c2;
             d2[0] = l2[0];
             d2[1] = l2[1];
             if (a.nlev > 3 && (rg & 1)) {
               const int c3 = (x0 >> 3) + tile;
-              half_t* d3 = a.lv[3] + (p1g * (gd.R >> 1) + (rg >> 1)) * gd.w3p + c3;
+              const BlockedDims::Slab s3 = gd.slab23(3, es, p1_0 + sp1);
+              half_t* d3 = a.lv[3] + s3.base + (rg >> 1) * s3.pitch + c3;
               const bool in = (rg >> 1) < (a.h >> 3) && c3 < (a.w >> 3);
               d3[0] = in ? pool4(l2prev[0], l2prev[1], l2[0], l2[1]) : (half_t)0;
               if (c3 + 1 == 4 * gd.S)  // the last column any thread owns: the pitch's padding is its to clear

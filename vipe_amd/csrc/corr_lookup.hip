@@ -11,9 +11,11 @@
 // update `corr += s * w` is one fused multiply-add (the contraction nvcc applies to that statement).
 // Out-of-bounds taps are skipped in the reference; adding their +-0 products instead is bit-identical
 // because an accumulator that starts at +0 can never hold -0.
-#include <stdlib.h>
+#include <algorithm>
+#include <type_traits>
 
 #include "common.cuh"
+#include "corr_layout.cuh"
 
 namespace {
 
@@ -53,31 +55,61 @@ struct Acc<double> {
   static __device__ __forceinline__ double store(reg v) { return v; }
 };
 
+// Tap setup of one pixel at pyramid level l (0 for a plain volume): the (2R+2)^2 integer taps (bx + i, by + j) around
+// floor(coords / 2**l) and the four bilinear weights.  The weights are a separate step because their rounding barrier
+// is not dead code to the compiler: a caller that only needs the window origin does not ask for them.
+template <typename T, int R>
+struct Taps {
+  using A = Acc<T>;
+  using reg = typename A::reg;
+  struct Weights { reg w00, w01, w10, w11; };
+  float dx, dy;
+  int bx, by;  // window origin
+  __device__ __forceinline__ Taps(float cx, float cy, int l) {
+    const float sc = 1.0f / (float)(1 << l);  // coords / 2**l is exact (droid_net.py:78)
+    const float x0 = cx * sc, y0 = cy * sc;
+    const float fx = floorf(x0), fy = floorf(y0);
+    dx = x0 - fx, dy = y0 - fy;
+    bx = (int)fx - R, by = (int)fy - R;
+  }
+  __device__ __forceinline__ int sh() const { return bx & 7; }  // tap column bx within its 8-column chunk bx >> 3
+  __device__ __forceinline__ Weights weights() const {
+    Weights w;
+    w.w11 = A::weight(dx * dy);                    // tap (i,j) -> out[i-1][j-1]
+    w.w10 = A::weight(dx * (1.0f - dy));           // tap (i,j) -> out[i-1][j]
+    w.w01 = A::weight((1.0f - dx) * dy);           // tap (i,j) -> out[i][j-1]
+    w.w00 = A::weight((1.0f - dx) * (1.0f - dy));  // tap (i,j) -> out[i][j]
+    return w;
+  }
+};
+
+// zero channels [from, to) of one pixel's channel row (the padding behind the looked-up channels), split among `lanes`
+// lanes of which this is number `lane`
+template <typename T>
+__device__ __forceinline__ void zero_channels(T* px, int from, int to, int lane = 0, int lanes = 1) {
+  for (int q = from + lane; q < to; q += lanes) px[q] = (T)0;
+}
+
 // One pixel, one level.  R = radius (compile-time for full unrolling), RD = 2R+1.
 template <typename T, int R>
-__device__ __forceinline__ void lookup_pixel(const T* __restrict__ slab, int h2, int w2, float x0, float y0,
+__device__ __forceinline__ void lookup_pixel(const T* __restrict__ slab, int h2, int w2, float cx, float cy, int l,
                                              T* __restrict__ out, int64_t out_stride) {
   constexpr int RD = 2 * R + 1;
   using A = Acc<T>;
   using reg = typename A::reg;
-  const float fx = floorf(x0), fy = floorf(y0);
-  const float dx = x0 - fx, dy = y0 - fy;
-  const int bx = (int)fx - R, by = (int)fy - R;
-  const reg w11 = A::weight(dx * dy);                  // tap (i,j) -> out[i-1][j-1]
-  const reg w10 = A::weight(dx * (1.0f - dy));         // tap (i,j) -> out[i-1][j]
-  const reg w01 = A::weight((1.0f - dx) * dy);         // tap (i,j) -> out[i][j-1]
-  const reg w00 = A::weight((1.0f - dx) * (1.0f - dy));// tap (i,j) -> out[i][j]
+  const Taps<T, R> t(cx, cy, l);
+  const auto [w00, w01, w10, w11] = t.weights();
 
-  // taps: s[i][j] = slab[by + j][bx + i]   (i <-> x, j <-> y), zero outside the map
+  // taps: s[i][j] = slab[t.by + j][t.bx + i]   (i <-> x, j <-> y), zero outside the map
   reg s[RD + 1][RD + 1];
 #pragma unroll
   for (int j = 0; j <= RD; ++j) {
-    const int y1 = by + j;
+    const int y1 = t.by + j;
     const bool yin = (y1 >= 0) & (y1 < h2);
     const T* row = slab + (int64_t)(yin ? y1 : 0) * w2;
 #pragma unroll
     for (int i = 0; i <= RD; ++i) {
-      const int x1 = bx + i;
+      const int x1 = t.bx + i;
       const bool in = yin & (x1 >= 0) & (x1 < w2);
       s[i][j] = in ? A::load(row + x1) : (reg)0;
     }
@@ -111,7 +143,7 @@ __global__ __launch_bounds__(256) void corr_index_forward_kernel(const T* __rest
   constexpr int RD = 2 * R + 1;
   const T* slab = volume + ((int64_t)n * P + p) * ((int64_t)h2 * w2);
   T* out = corr + (int64_t)n * RD * RD * P + p;
-  lookup_pixel<T, R>(slab, h2, w2, x0, y0, out, P);
+  lookup_pixel<T, R>(slab, h2, w2, x0, y0, 0, out, P);
 }
 
 struct LevelPtrs {
@@ -130,18 +162,16 @@ __global__ __launch_bounds__(256) void corr_pyramid_lookup_kernel(LevelPtrs lv, 
   const int l = blockIdx.z;
   if (p >= P) return;
   const float2 c = reinterpret_cast<const float2*>(coords)[(int64_t)n * P + p];
-  const float sc = 1.0f / (float)(1 << l);  // coords / 2**l is exact (droid_net.py:78)
   const int h2l = h2 >> l, w2l = w2 >> l;
   constexpr int RD = 2 * R + 1;
   const T* slab = reinterpret_cast<const T*>(lv.p[l]) + ((int64_t)n * P + p) * ((int64_t)h2l * w2l);
   if (nhwc_stride > 0) {
-    T* o = out + ((int64_t)n * P + p) * nhwc_stride + l * (RD * RD);
-    lookup_pixel<T, R>(slab, h2l, w2l, c.x * sc, c.y * sc, o, 1);
-    if (l == L - 1)
-      for (int q = L * RD * RD; q < nhwc_stride; ++q) out[((int64_t)n * P + p) * nhwc_stride + q] = (T)0;
+    T* px = out + ((int64_t)n * P + p) * nhwc_stride;
+    lookup_pixel<T, R>(slab, h2l, w2l, c.x, c.y, l, px + l * (RD * RD), 1);
+    if (l == L - 1) zero_channels(px, L * RD * RD, nhwc_stride);
   } else {
     T* o = out + ((int64_t)n * L + l) * (RD * RD) * P + p;
-    lookup_pixel<T, R>(slab, h2l, w2l, c.x * sc, c.y * sc, o, P);
+    lookup_pixel<T, R>(slab, h2l, w2l, c.x, c.y, l, o, P);
   }
 }
 
@@ -154,6 +184,42 @@ __global__ __launch_bounds__(256) void corr_pyramid_lookup_kernel(LevelPtrs lv, 
 typedef unsigned uint4v __attribute__((ext_vector_type(4)));
 
 typedef _Float16 half2v __attribute__((ext_vector_type(2)));
+
+// ---- the two aligned 16-byte chunks of tap row y1 that cover columns [8 c0, 8 c0 + 16) of source pixel pc's level-l slab
+// in `slot` of the level buffer `base`, zero outside the map.  The layout decides where a chunk lives and how many a row has.
+template <bool BLK>  // BLK: VIPE_PYRAMID_BLOCKED (source grid == target grid, padded: d), else level l = [slot][P][h2 >> l][w2 >> l]
+struct PyrLayout {
+  int P, h2, w2;
+  BlockedDims d;
+  __device__ __forceinline__ PyrLayout(int P_, int h2_, int w2_) : P(P_), h2(h2_), w2(w2_), d(h2_, w2_) {}
+};
+
+struct RowPair { uint4v lo, hi; };
+
+template <bool BLK>
+__device__ __forceinline__ RowPair gather_row(const void* base, const PyrLayout<BLK>& lay, int l, int64_t slot, int pc,
+                                              int y1, int c0) {
+  const half_t* lvl = reinterpret_cast<const half_t*>(base);
+  const int h2l = lay.h2 >> l, w2l = lay.w2 >> l;
+  // 8-column pieces of a row: whole ones in the reference layout; in the blocked layout the last one may be partial
+  // (columns >= w2l stored as zero by the build kernel)
+  const int nchunks = BLK ? (w2l + 7) >> 3 : w2l >> 3;
+  const bool rowok = (y1 >= 0) & (y1 < h2l);
+  const int yr = rowok ? y1 : 0;
+  // one slab per source pixel (reference layout; levels 2 / 3 of the blocked layout, padded): the row's chunks are
+  // contiguous and its address is formed before the bounds tests.  Levels 0 / 1 of the blocked layout are tiled
+  const bool tiled = BLK && l < 2;
+  const uint4v* rowp = nullptr;
+  if (!tiled) {
+    const BlockedDims::Slab s = BLK ? lay.d.slab23(l, slot, pc) : BlockedDims::Slab{(slot * lay.P + pc) * ((int64_t)h2l * w2l), h2l, w2l};
+    rowp = reinterpret_cast<const uint4v*>(lvl + s.base + (int64_t)yr * s.pitch);
+  }
+  auto piece = [&](int c) { return tiled ? *reinterpret_cast<const uint4v*>(lvl + lay.d.piece01(l, slot, pc, yr, c)) : rowp[c]; };
+  RowPair r = {uint4v{0, 0, 0, 0}, uint4v{0, 0, 0, 0}};
+  if (rowok & (c0 >= 0) & (c0 < nchunks)) r.lo = piece(c0);
+  if (rowok & (c0 + 1 >= 0) & (c0 + 1 < nchunks)) r.hi = piece(c0 + 1);
+  return r;
+}
 
 // The 7 outputs out[a][j], a = 0..6, of ONE tap row j of one level, in packed fp16 arithmetic.  d[0..7]: the two aligned
 // 16-byte chunks of row y = by + j (zero outside the map), sh = (bx & 7): taps t[i] = halves d[sh + i], i = 0..7; the taps
@@ -196,7 +262,6 @@ __global__ __launch_bounds__(256) void corr_pyramid_lookup_rows_kernel(LevelPtrs
                                                                        half_t* __restrict__ out, int h1, int w1, int h2,
                                                                        int w2, int L, int nhwc_stride) {
   constexpr int R = 3, RD = 7;
-  using A = Acc<half_t>;
   const int P = h1 * w1;
   const int j = threadIdx.x & 7;                         // tap row
   const int p = blockIdx.x * 32 + (threadIdx.x >> 3);    // pixel
@@ -204,28 +269,12 @@ __global__ __launch_bounds__(256) void corr_pyramid_lookup_rows_kernel(LevelPtrs
   const bool pok = p < P;
   const int pc = pok ? p : P - 1;
   const float2 c = reinterpret_cast<const float2*>(coords)[(int64_t)n * P + pc];
-  const float sc = 1.0f / (float)(1 << l);
-  const float x0 = c.x * sc, y0 = c.y * sc;
-  const int h2l = h2 >> l, w2l = w2 >> l;
-  const float fx = floorf(x0), fy = floorf(y0);
-  const float dx = x0 - fx, dy = y0 - fy;
-  const int bx = (int)fx - R, by = (int)fy - R;
-  const float w11 = A::weight(dx * dy), w10 = A::weight(dx * (1.0f - dy));
-  const float w01 = A::weight((1.0f - dx) * dy), w00 = A::weight((1.0f - dx) * (1.0f - dy));
-
-  // two aligned chunks of row y1 covering x in [8*c0, 8*c0 + 16)
-  const int y1 = by + j;
-  const int c0 = bx >> 3, sh = bx & 7;
-  const int nchunks = w2l >> 3;
-  const bool rowok = (y1 >= 0) & (y1 < h2l);
-  const half_t* slab = reinterpret_cast<const half_t*>(lv.p[l]) + ((int64_t)n * P + pc) * ((int64_t)h2l * w2l);
-  const uint4v* rowp = reinterpret_cast<const uint4v*>(slab + (int64_t)(rowok ? y1 : 0) * w2l);
-  uint4v lo = {0, 0, 0, 0}, hi = {0, 0, 0, 0};
-  if (rowok & (c0 >= 0) & (c0 < nchunks)) lo = rowp[c0];
-  if (rowok & (c0 + 1 >= 0) & (c0 + 1 < nchunks)) hi = rowp[c0 + 1];
-  const unsigned d[8] = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
+  const Taps<half_t, R> t(c.x, c.y, l);
+  const auto [w00, w01, w10, w11] = t.weights();
+  const RowPair r = gather_row(lv.p[l], PyrLayout<false>(P, h2, w2), l, n, pc, t.by + j, t.bx >> 3);
+  const unsigned d[8] = {r.lo[0], r.lo[1], r.lo[2], r.lo[3], r.hi[0], r.hi[1], r.hi[2], r.hi[3]};
   half2v o[4];
-  row_outputs_pk(d, sh, w00, w01, w10, w11, o);
+  row_outputs_pk(d, t.sh(), w00, w01, w10, w11, o);
   if (!pok || j >= RD) return;
 #pragma unroll
   for (int a = 0; a < RD; ++a) {
@@ -234,8 +283,7 @@ __global__ __launch_bounds__(256) void corr_pyramid_lookup_rows_kernel(LevelPtrs
     if (nhwc_stride > 0) out[((int64_t)n * P + p) * nhwc_stride + ch] = v;
     else out[((int64_t)n * L * (RD * RD) + ch) * P + p] = v;
   }
-  if (nhwc_stride > 0 && l == L - 1 && j == 0)
-    for (int qq = L * RD * RD; qq < nhwc_stride; ++qq) out[((int64_t)n * P + p) * nhwc_stride + qq] = (half_t)0;
+  if (nhwc_stride > 0 && l == L - 1 && j == 0) zero_channels(out + ((int64_t)n * P + p) * nhwc_stride, L * RD * RD, nhwc_stride);
 }
 
 // ---- channels-last, 4 levels in one workgroup: the 8 loads of a lane (2 per level) are issued back to back (4x the
@@ -244,11 +292,38 @@ __global__ __launch_bounds__(256) void corr_pyramid_lookup_rows_kernel(LevelPtrs
 // 437 MB of HBM writes for 339 MB of output at E = 276).  Same taps, weights and addition chains as above.
 constexpr int LK4_PITCH = 208;  // halves per staged pixel (16-byte aligned rows)
 
+// Tap row j of all 4 levels of source pixel pc (coords c) -> channels 0..195 of row pl of `stage` (PITCH halves per
+// pixel).  Two phases: first all 8 loads of the lane, then the arithmetic - interleaved, each level's loads would wait
+// behind the previous level's arithmetic.
+template <int PITCH, bool BLK>
+__device__ __forceinline__ void lookup4_to_lds(const LevelPtrs& lv, const PyrLayout<BLK>& lay, int64_t slot, int pc, float2 c,
+                                               int j, half_t* __restrict__ stage, int pl) {
+  constexpr int R = 3, RD = 7, L = 4;
+  uint4v lo[L], hi[L];
+#pragma unroll
+  for (int l = 0; l < L; ++l) {
+    const Taps<half_t, R> t(c.x, c.y, l);
+    const RowPair r = gather_row(lv.p[l], lay, l, slot, pc, t.by + j, t.bx >> 3);
+    lo[l] = r.lo, hi[l] = r.hi;
+  }
+#pragma unroll
+  for (int l = 0; l < L; ++l) {
+    const Taps<half_t, R> t(c.x, c.y, l);
+    const auto [w00, w01, w10, w11] = t.weights();
+    const unsigned d[8] = {lo[l][0], lo[l][1], lo[l][2], lo[l][3], hi[l][0], hi[l][1], hi[l][2], hi[l][3]};
+    half2v o[4];
+    row_outputs_pk(d, t.sh(), w00, w01, w10, w11, o);
+    if (j < RD) {
+#pragma unroll
+      for (int a = 0; a < RD; ++a) stage[pl * PITCH + l * (RD * RD) + a * RD + j] = o[a >> 1][a & 1];
+    }
+  }
+}
+
 __global__ __launch_bounds__(256) void corr_pyramid_lookup_rows4_kernel(LevelPtrs lv, const float* __restrict__ coords,
                                                                         half_t* __restrict__ out, int h1, int w1, int h2,
                                                                         int w2, int nhwc_stride) {
-  constexpr int R = 3, RD = 7, L = 4;
-  using A = Acc<half_t>;
+  constexpr int RD = 7, L = 4;
   __shared__ __align__(16) half_t stage[32 * LK4_PITCH];
   const int P = h1 * w1;
   const int j = threadIdx.x & 7;       // tap row
@@ -258,39 +333,8 @@ __global__ __launch_bounds__(256) void corr_pyramid_lookup_rows4_kernel(LevelPtr
   const bool pok = p < P;
   const int pc = pok ? p : P - 1;
   const float2 c = reinterpret_cast<const float2*>(coords)[(int64_t)n * P + pc];
-  uint4v lo[L], hi[L];
-#pragma unroll
-  for (int l = 0; l < L; ++l) {
-    const float sc = 1.0f / (float)(1 << l);
-    const int h2l = h2 >> l, w2l = w2 >> l;
-    const int bx = (int)floorf(c.x * sc) - R, by = (int)floorf(c.y * sc) - R;
-    const int y1 = by + j, c0 = bx >> 3, nchunks = w2l >> 3;
-    const bool rowok = (y1 >= 0) & (y1 < h2l);
-    const half_t* slab = reinterpret_cast<const half_t*>(lv.p[l]) + ((int64_t)n * P + pc) * ((int64_t)h2l * w2l);
-    const uint4v* rowp = reinterpret_cast<const uint4v*>(slab + (int64_t)(rowok ? y1 : 0) * w2l);
-    lo[l] = uint4v{0, 0, 0, 0};
-    hi[l] = uint4v{0, 0, 0, 0};
-    if (rowok & (c0 >= 0) & (c0 < nchunks)) lo[l] = rowp[c0];
-    if (rowok & (c0 + 1 >= 0) & (c0 + 1 < nchunks)) hi[l] = rowp[c0 + 1];
-  }
-#pragma unroll
-  for (int l = 0; l < L; ++l) {
-    const float sc = 1.0f / (float)(1 << l);
-    const float x0 = c.x * sc, y0 = c.y * sc;
-    const float fx = floorf(x0), fy = floorf(y0);
-    const float dx = x0 - fx, dy = y0 - fy;
-    const int sh = ((int)fx - R) & 7;
-    const float w11 = A::weight(dx * dy), w10 = A::weight(dx * (1.0f - dy));
-    const float w01 = A::weight((1.0f - dx) * dy), w00 = A::weight((1.0f - dx) * (1.0f - dy));
-    const unsigned d[8] = {lo[l][0], lo[l][1], lo[l][2], lo[l][3], hi[l][0], hi[l][1], hi[l][2], hi[l][3]};
-    half2v o[4];
-    row_outputs_pk(d, sh, w00, w01, w10, w11, o);
-    if (j < RD) {
-#pragma unroll
-      for (int a = 0; a < RD; ++a) stage[pl * LK4_PITCH + l * (RD * RD) + a * RD + j] = o[a >> 1][a & 1];
-    }
-  }
-  if (j < 4) stage[pl * LK4_PITCH + L * RD * RD + j] = (half_t)0;
+  lookup4_to_lds<LK4_PITCH>(lv, PyrLayout<false>(P, h2, w2), n, pc, c, j, stage, pl);
+  zero_channels(stage + pl * LK4_PITCH, L * RD * RD, L * RD * RD + 4, j, 8);
   __syncthreads();
   // 16-byte pieces of the staged pixels: nhwc_stride / 8 per pixel
   const int cpp = nhwc_stride >> 3;
@@ -320,8 +364,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
     LevelPtrs lv, const float* __restrict__ coords, const half_t* __restrict__ wpk, const float* __restrict__ bias,
     half_t* __restrict__ out, int out_ctot, int out_coff, int h1, int w1, int h2, int w2, int B, int cout_pad, int act,
     const int* __restrict__ slots) {
-  constexpr int R = 3, RD = 7, L = 4;
-  using A = Acc<half_t>;
+  constexpr int RD = 7, L = 4;
   __shared__ __align__(16) half_t stage[32 * LKC_PITCH];
   __shared__ __align__(16) half_t ostage[32 * LKC_OPITCH];
   const int P = h1 * w1;
@@ -330,8 +373,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
   const int l16 = lane & 15, kg = lane >> 4;
   const int gpp = (P + 31) / 32;
   const int ngroups = B * gpp;
-  // padded blocked layout (include/vipe_amd.h): G groups of 64 source pixels, S strips of 32 columns, R row groups of 4
-  const int bG = (P + 63) >> 6, bS = (w2 + 31) >> 5, bR = ((h2 + 7) >> 3) << 1;
+  const PyrLayout<BLK> lay(P, h2, w2);
   // this wave's weights: couts 32 wave + 16 i + l16, k = 32 s + 8 kg .. + 7  (packed [k / 64][cout_pad][64])
   half8v af[2][7];
 #pragma unroll
@@ -345,8 +387,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
 #pragma unroll
   for (int i = 0; i < 2; ++i) bv[i] = *reinterpret_cast<const float4*>(bias + 32 * wave + 16 * i + 4 * kg);
   // zero the k padding of the staged rows once (columns 196..231 are never written by the lookup)
-  for (int i = tid; i < 32 * (LKC_PITCH - L * RD * RD); i += 256)
-    stage[(i / (LKC_PITCH - L * RD * RD)) * LKC_PITCH + L * RD * RD + i % (LKC_PITCH - L * RD * RD)] = (half_t)0;
+  zero_channels(stage + pl * LKC_PITCH, L * RD * RD, LKC_PITCH, j, 8);
 
   for (int grp = blockIdx.x; grp < ngroups; grp += gridDim.x) {
     const int n = grp / gpp, p = (grp % gpp) * 32 + pl;
@@ -354,62 +395,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
     const int pc = pok ? p : P - 1;
     const float2 c = reinterpret_cast<const float2*>(coords)[(int64_t)n * P + pc];
     const int ns = slots ? slots[n] : n;  // pooled pyramids: edge n lives in slot slots[n] of the level buffers
-    uint4v lo[L], hi[L];
-#pragma unroll
-    for (int l = 0; l < L; ++l) {
-      const float sc = 1.0f / (float)(1 << l);
-      const int h2l = h2 >> l, w2l = w2 >> l;
-      const int bx = (int)floorf(c.x * sc) - R, by = (int)floorf(c.y * sc) - R;
-      const int y1 = by + j, c0 = bx >> 3;
-      // 8-column pieces of a row: whole ones in the reference layout; in the blocked layout the last one may be partial
-      // (columns >= w2l stored as zero by the build kernel)
-      const int nchunks = BLK ? (w2l + 7) >> 3 : w2l >> 3;
-      const bool rowok = (y1 >= 0) & (y1 < h2l);
-      lo[l] = uint4v{0, 0, 0, 0};
-      hi[l] = uint4v{0, 0, 0, 0};
-#ifdef VIPE_LOOKUP_SKIP_LEVEL  // measurement builds only (scratch/build_variant_src.sh): what the loads of one level cost
-      if (l == VIPE_LOOKUP_SKIP_LEVEL) continue;
-#endif
-      if (BLK && l < 2) {
-        // VIPE_PYRAMID_BLOCKED (include/vipe_amd.h): 16-byte piece (row y1, columns 8 c ..) of source pixel pc lives in
-        // run ((x-strip) * (R >> l) + y1 / 4) of the pixel's group of 64, tile c % T, tile row y1 % 4
-        const int T = 4 >> l, rgs = bR >> l;
-        const int64_t eg = (int64_t)ns * bG + (pc >> 6);
-        const half_t* base = reinterpret_cast<const half_t*>(lv.p[l]);
-        const int yr = rowok ? y1 : 0;
-        auto piece = [&](int cc) {
-          const int64_t run = eg * ((int64_t)rgs * bS) + (cc / T) * rgs + (yr >> 2);
-          return *reinterpret_cast<const uint4v*>(base + (run * 64 + (pc & 63)) * (T * 32) + (cc % T) * 32 + (yr & 3) * 8);
-        };
-        if (rowok & (c0 >= 0) & (c0 < nchunks)) lo[l] = piece(c0);
-        if (rowok & (c0 + 1 >= 0) & (c0 + 1 < nchunks)) hi[l] = piece(c0 + 1);
-      } else {
-        // one slab per source pixel: [h >> l][w >> l] (reference), or levels 2 / 3 of the blocked layout - a slab for every
-        // pixel of every group of 64, R >> (l - 2) rows of 8 S / round_up(4 S, 8) entries
-        const int hlp = BLK ? bR >> (l - 2) : h2l, wlp = BLK ? (l == 2 ? 8 * bS : ((4 * bS + 7) & ~7)) : w2l;
-        const half_t* slab = reinterpret_cast<const half_t*>(lv.p[l]) + ((int64_t)ns * (BLK ? bG * 64 : P) + pc) * ((int64_t)hlp * wlp);
-        const uint4v* rowp = reinterpret_cast<const uint4v*>(slab + (int64_t)(rowok ? y1 : 0) * wlp);
-        if (rowok & (c0 >= 0) & (c0 < nchunks)) lo[l] = rowp[c0];
-        if (rowok & (c0 + 1 >= 0) & (c0 + 1 < nchunks)) hi[l] = rowp[c0 + 1];
-      }
-    }
-#pragma unroll
-    for (int l = 0; l < L; ++l) {
-      const float sc = 1.0f / (float)(1 << l);
-      const float x0 = c.x * sc, y0 = c.y * sc;
-      const float fx = floorf(x0), fy = floorf(y0);
-      const float dx = x0 - fx, dy = y0 - fy;
-      const int sh = ((int)fx - R) & 7;
-      const float w11 = A::weight(dx * dy), w10 = A::weight(dx * (1.0f - dy));
-      const float w01 = A::weight((1.0f - dx) * dy), w00 = A::weight((1.0f - dx) * (1.0f - dy));
-      const unsigned d[8] = {lo[l][0], lo[l][1], lo[l][2], lo[l][3], hi[l][0], hi[l][1], hi[l][2], hi[l][3]};
-      half2v o[4];
-      row_outputs_pk(d, sh, w00, w01, w10, w11, o);
-      if (j < RD) {
-#pragma unroll
-        for (int a = 0; a < RD; ++a) stage[pl * LKC_PITCH + l * (RD * RD) + a * RD + j] = o[a >> 1][a & 1];
-      }
-    }
+    lookup4_to_lds<LKC_PITCH>(lv, lay, ns, pc, c, j, stage, pl);
     __syncthreads();
     // ---- 1x1 convolution of the 32 staged pixels: D[cout, pixel]
     float4v acc[2][2];
@@ -467,11 +453,8 @@ __global__ __launch_bounds__(256) void corr_index_backward_kernel(const float* _
   if (p >= P) return;
   const float x0 = coords[((int64_t)n * 2 + 0) * P + p];
   const float y0 = coords[((int64_t)n * 2 + 1) * P + p];
-  const float fx = floorf(x0), fy = floorf(y0);
-  const float dx = x0 - fx, dy = y0 - fy;
-  const int bx = (int)fx - R, by = (int)fy - R;
-  const reg w11 = A::weight(dx * dy), w10 = A::weight(dx * (1.0f - dy));
-  const reg w01 = A::weight((1.0f - dx) * dy), w00 = A::weight((1.0f - dx) * (1.0f - dy));
+  const Taps<T, R> t(x0, y0, 0);
+  const auto [w00, w01, w10, w11] = t.weights();
   const T* g = corr_grad + (int64_t)n * RD * RD * P + p;
   T* slab = volume_grad + ((int64_t)n * P + p) * ((int64_t)h2 * w2);
   reg cg[RD][RD];
@@ -483,7 +466,7 @@ __global__ __launch_bounds__(256) void corr_index_backward_kernel(const float* _
   for (int i = 0; i <= RD; ++i) {
 #pragma unroll
     for (int j = 0; j <= RD; ++j) {
-      const int x1 = bx + i, y1 = by + j;
+      const int x1 = t.bx + i, y1 = t.by + j;
       if ((y1 >= 0) & (y1 < h2) & (x1 >= 0) & (x1 < w2)) {
         reg acc = (reg)0;  // correlation_kernels.cu:100-107 order
         if (i > 0 && j > 0) acc = A::madd(acc, cg[i - 1][j - 1], w11);
@@ -496,46 +479,21 @@ __global__ __launch_bounds__(256) void corr_index_backward_kernel(const float* _
   }
 }
 
-template <typename T>
-int launch_fwd(const void* vol, const float* coords, void* corr, int B, int h1, int w1, int h2, int w2, int r,
-               hipStream_t s) {
-  dim3 grid((h1 * w1 + 255) / 256, B), block(256);
-  switch (r) {
-    case 1: corr_index_forward_kernel<T, 1><<<grid, block, 0, s>>>((const T*)vol, coords, (T*)corr, h1, w1, h2, w2); break;
-    case 2: corr_index_forward_kernel<T, 2><<<grid, block, 0, s>>>((const T*)vol, coords, (T*)corr, h1, w1, h2, w2); break;
-    case 3: corr_index_forward_kernel<T, 3><<<grid, block, 0, s>>>((const T*)vol, coords, (T*)corr, h1, w1, h2, w2); break;
-    case 4: corr_index_forward_kernel<T, 4><<<grid, block, 0, s>>>((const T*)vol, coords, (T*)corr, h1, w1, h2, w2); break;
-    default: return VIPE_EUNSUPPORTED;
-  }
-  return vipe_launch_status();
+// launch(std::integral_constant<int, r>) if r is one of the radii Rs (the instantiated ones), then the launch status
+template <int... Rs, typename F>
+int for_radius(int r, F&& launch) {
+  const bool hit = ((r == Rs && (launch(std::integral_constant<int, Rs>{}), true)) || ...);
+  return hit ? vipe_launch_status() : VIPE_EUNSUPPORTED;
 }
 
-template <typename T>
-int launch_bwd(const float* coords, const void* cg, void* vg, int B, int h1, int w1, int h2, int w2, int r,
-               hipStream_t s) {
-  hipError_t e = hipMemsetAsync(vg, 0, sizeof(T) * (size_t)B * h1 * w1 * h2 * w2, s);
-  if (e != hipSuccess) return (int)e;
-  dim3 grid((h1 * w1 + 255) / 256, B), block(256);
-  switch (r) {
-    case 1: corr_index_backward_kernel<T, 1><<<grid, block, 0, s>>>(coords, (const T*)cg, (T*)vg, h1, w1, h2, w2); break;
-    case 2: corr_index_backward_kernel<T, 2><<<grid, block, 0, s>>>(coords, (const T*)cg, (T*)vg, h1, w1, h2, w2); break;
-    case 3: corr_index_backward_kernel<T, 3><<<grid, block, 0, s>>>(coords, (const T*)cg, (T*)vg, h1, w1, h2, w2); break;
-    case 4: corr_index_backward_kernel<T, 4><<<grid, block, 0, s>>>(coords, (const T*)cg, (T*)vg, h1, w1, h2, w2); break;
-    default: return VIPE_EUNSUPPORTED;
-  }
-  return vipe_launch_status();
-}
-
-template <typename T>
-int launch_pyr(const LevelPtrs& lv, const float* coords, void* out, int B, int h1, int w1, int h2, int w2, int L,
-               int r, int nhwc_stride, hipStream_t s) {
-  dim3 grid((h1 * w1 + 255) / 256, B, L), block(256);
-  switch (r) {
-    case 3: corr_pyramid_lookup_kernel<T, 3><<<grid, block, 0, s>>>(lv, coords, (T*)out, h1, w1, h2, w2, L, nhwc_stride); break;
-    case 4: corr_pyramid_lookup_kernel<T, 4><<<grid, block, 0, s>>>(lv, coords, (T*)out, h1, w1, h2, w2, L, nhwc_stride); break;
-    default: return VIPE_EUNSUPPORTED;
-  }
-  return vipe_launch_status();
+// f(T{}) for the storage type T of a VIPE_F* code
+template <bool WITH_F64, typename F>
+int for_dtype(int dtype, F&& f) {
+  if (dtype == VIPE_F16) return f(half_t{});
+  if (dtype == VIPE_F32) return f(float{});
+  if constexpr (WITH_F64)
+    if (dtype == VIPE_F64) return f(double{});
+  return VIPE_EINVAL;
 }
 
 }  // namespace
@@ -545,13 +503,14 @@ VIPE_EXPORT int vipe_corr_index_forward(const void* d_volume, const float* d_coo
   VIPE_CHECK_ARG(B >= 0 && h1 > 0 && w1 > 0 && h2 > 0 && w2 > 0 && B <= 65535);
   if (B == 0) return VIPE_OK;
   VIPE_CHECK_ARG(d_volume && d_coords && d_corr);
-  hipStream_t s = as_stream(stream);
-  switch (dtype) {
-    case VIPE_F16: return launch_fwd<half_t>(d_volume, d_coords, d_corr, B, h1, w1, h2, w2, radius, s);
-    case VIPE_F32: return launch_fwd<float>(d_volume, d_coords, d_corr, B, h1, w1, h2, w2, radius, s);
-    case VIPE_F64: return launch_fwd<double>(d_volume, d_coords, d_corr, B, h1, w1, h2, w2, radius, s);
-  }
-  return VIPE_EINVAL;
+  const dim3 grid((h1 * w1 + 255) / 256, B);
+  return for_dtype<true>(dtype, [&](auto t) {
+    using T = decltype(t);
+    return for_radius<1, 2, 3, 4>(radius, [&](auto r) {
+      corr_index_forward_kernel<T, decltype(r)::value><<<grid, 256, 0, as_stream(stream)>>>(
+          (const T*)d_volume, d_coords, (T*)d_corr, h1, w1, h2, w2);
+    });
+  });
 }
 
 VIPE_EXPORT int vipe_corr_index_backward(const float* d_coords, const void* d_corr_grad, void* d_volume_grad, int B,
@@ -560,12 +519,16 @@ VIPE_EXPORT int vipe_corr_index_backward(const float* d_coords, const void* d_co
   if (B == 0) return VIPE_OK;
   VIPE_CHECK_ARG(d_coords && d_corr_grad && d_volume_grad);
   hipStream_t s = as_stream(stream);
-  switch (dtype) {
-    case VIPE_F16: return launch_bwd<half_t>(d_coords, d_corr_grad, d_volume_grad, B, h1, w1, h2, w2, radius, s);
-    case VIPE_F32: return launch_bwd<float>(d_coords, d_corr_grad, d_volume_grad, B, h1, w1, h2, w2, radius, s);
-    case VIPE_F64: return launch_bwd<double>(d_coords, d_corr_grad, d_volume_grad, B, h1, w1, h2, w2, radius, s);
-  }
-  return VIPE_EINVAL;
+  const dim3 grid((h1 * w1 + 255) / 256, B);
+  return for_dtype<true>(dtype, [&](auto t) {
+    using T = decltype(t);
+    hipError_t e = hipMemsetAsync(d_volume_grad, 0, sizeof(T) * (size_t)B * h1 * w1 * h2 * w2, s);
+    if (e != hipSuccess) return (int)e;
+    return for_radius<1, 2, 3, 4>(radius, [&](auto r) {
+      corr_index_backward_kernel<T, decltype(r)::value><<<grid, 256, 0, s>>>(d_coords, (const T*)d_corr_grad,
+                                                                             (T*)d_volume_grad, h1, w1, h2, w2);
+    });
+  });
 }
 
 static int pyramid_lookup_impl(const void* const* h_levels, const float* d_coords, void* d_out, int B, int h1, int w1,
@@ -586,16 +549,18 @@ static int pyramid_lookup_impl(const void* const* h_levels, const float* d_coord
                                                                                    h2, w2, nhwc_stride);
       return vipe_launch_status();
     }
-    dim3 grid((h1 * w1 + 31) / 32, B, num_levels);
-    corr_pyramid_lookup_rows_kernel<<<grid, 256, 0, s>>>(lv, d_coords, (half_t*)d_out, h1, w1, h2, w2, num_levels,
-                                                          nhwc_stride);
+    corr_pyramid_lookup_rows_kernel<<<dim3((h1 * w1 + 31) / 32, B, num_levels), 256, 0, s>>>(
+        lv, d_coords, (half_t*)d_out, h1, w1, h2, w2, num_levels, nhwc_stride);
     return vipe_launch_status();
   }
-  switch (dtype) {
-    case VIPE_F16: return launch_pyr<half_t>(lv, d_coords, d_out, B, h1, w1, h2, w2, num_levels, radius, nhwc_stride, s);
-    case VIPE_F32: return launch_pyr<float>(lv, d_coords, d_out, B, h1, w1, h2, w2, num_levels, radius, nhwc_stride, s);
-  }
-  return VIPE_EINVAL;
+  const dim3 grid((h1 * w1 + 255) / 256, B, num_levels);
+  return for_dtype<false>(dtype, [&](auto t) {
+    using T = decltype(t);
+    return for_radius<3, 4>(radius, [&](auto r) {
+      corr_pyramid_lookup_kernel<T, decltype(r)::value><<<grid, 256, 0, s>>>(lv, d_coords, (T*)d_out, h1, w1, h2, w2,
+                                                                             num_levels, nhwc_stride);
+    });
+  });
 }
 
 VIPE_EXPORT int vipe_corr_pyramid_lookup(const void* const* h_levels, const float* d_coords, void* d_out, int B,
@@ -635,13 +600,11 @@ VIPE_EXPORT int vipe_corr_lookup_conv1x1(const void* const* h_levels, const floa
   }
   const int64_t ngroups = (int64_t)B * ((h1 * w1 + 31) / 32);
   const int blocks = (int)std::min<int64_t>(ngroups, 256 * 4);
-  if (layout == VIPE_PYRAMID_BLOCKED)
-    corr_lookup_conv_kernel<true><<<blocks, 256, 0, as_stream(stream)>>>(lv, d_coords, (const half_t*)d_w_packed, d_bias,
-                                                                         (half_t*)d_out, out_ctot, out_coff, h1, w1, h2, w2,
-                                                                         B, 128, act, d_slots);
-  else
-    corr_lookup_conv_kernel<false><<<blocks, 256, 0, as_stream(stream)>>>(lv, d_coords, (const half_t*)d_w_packed, d_bias,
-                                                                          (half_t*)d_out, out_ctot, out_coff, h1, w1, h2, w2,
-                                                                          B, 128, act, d_slots);
+  auto launch = [&](auto blk) {
+    corr_lookup_conv_kernel<decltype(blk)::value><<<blocks, 256, 0, as_stream(stream)>>>(
+        lv, d_coords, (const half_t*)d_w_packed, d_bias, (half_t*)d_out, out_ctot, out_coff, h1, w1, h2, w2, B, 128, act, d_slots);
+  };
+  if (layout == VIPE_PYRAMID_BLOCKED) launch(std::true_type{});
+  else launch(std::false_type{});
   return vipe_launch_status();
 }
