@@ -233,7 +233,9 @@ int vipe_reproject_motion_nhwc(const float* d_poses, const float* d_disps, const
  *   (buffer.py:462-465); t0 == t1 fixes every pose.
  *   d_workspace: vipe_dense_ba_workspace_bytes(...) bytes, contents need not be initialised.
  *   d_info (optional, 8 ints): [n_free_poses, n_free_disp_frames, cholesky_failures, n_regular_unknowns,
- *   band width in 6x6 blocks, 1 if the LDS band solver solved the last iteration, largest source-frame degree, 0]. */
+ *   band width in 6x6 blocks, the solver of the last iteration (0 global-memory Cholesky, also when nothing was solved;
+ *   1 LDS band solver; 2 LDS dense solver), largest source-frame degree, 1 if a pivot of the last tiled factorisation
+ *   failed]. */
 /* Co-scheduling hook of vipe_dense_ba (optional).  Most of a Gauss-Newton iteration is the reduced-system solve: ONE
  * workgroup busy on a 256-CU part.  A caller with independent work (FactorGraph.update: the hidden-state part of the next
  * iteration's GRU gates, vipe_update_gate_state_piece) hands it over in `n_pieces = max(n_iters, 1)` pieces: piece k is

@@ -331,6 +331,7 @@ def test_dense_ba_rig_matches_reference_solver(name):
     assert info[2] == 0, "Cholesky must not fail"
     n_tail = (g.V * 1 if bk.get("optimize_intrinsics") else 0) + (6 * (g.V - 1) if bk.get("optimize_rig_rotation") else 0)
     assert info[3] == 6 * info[0] + n_tail
+    assert info[5] == 0, "rigs take the global-memory solver, whatever the band looks like"
     assert np.abs(p - rp).max() <= 1e-4 * max(1.0, np.abs(rp).max()), np.abs(p - rp).max()
     assert np.abs(d - rd).max() <= 1e-4 * np.abs(rd).max(), np.abs(d - rd).max() / np.abs(rd).max()
     assert np.abs(k - rk).max() <= 1e-4 * np.abs(rk).max()
@@ -1876,6 +1877,8 @@ def test_dense_window_solver_sizes(n_poses, intr, expect_lds_dense):
     assert info[0] == n_poses - 1 and info[3] == 6 * (n_poses - 1) + int(intr) and info[2] == 0
     if expect_lds_dense is not None:
         assert (info[5] == 2) == expect_lds_dense
+    if (n_poses, intr) == (28, False):
+        assert info[5] == 0  # n = 162: the single-workgroup global-memory kernel
     assert np.abs(p - op).max() <= 1e-4 * max(1.0, np.abs(op).max())
     assert np.abs(d - od[:, 0]).max() <= 1e-4 * np.abs(od).max()
     if intr:

@@ -14,7 +14,7 @@
 // Waves never wait for each other inside the walk: wave-private LDS, LDS float atomics into workgroup accumulators,
 // three workgroup barriers in total.  Exact fp32 products and sums (the f32 MFMA is an fmaf chain).
 // Handles source frames with at most AM_DMAX terms (the radius-3 neighbourhood graph: 6); ba_plan_kernel publishes
-// the largest degree in info[6] and exactly one of the two accumulate kernels runs.
+// the largest degree in info[INFO_MAX_DEGREE] and exactly one of the two accumulate kernels runs.
 constexpr int AM_ROWS = 48;             // R2 row capacity: 6 (AM_DMAX + 1) + F + 1 <= 48
 constexpr int AM_P1 = 130;              // float pitch of the R1 tile [16][128]   (= 2 mod 32: conflict-free b32 reads)
 constexpr int AM_P2 = 66;               // float pitch of the R2 image [48][64]
@@ -361,7 +361,7 @@ template <int CAM, int F>
 __global__ __launch_bounds__(TILE) __attribute__((amdgpu_waves_per_eu(3, 3))) void ba_accum_mfma_kernel(BAArgs a) {
   const vipe_ba_params& prm = a.p;
   const BAWs& w = a.w;
-  if (a.force_general || w.info[6] > AM_DMAX) return;  // force_general: the walk + Schur pair takes every graph (vipe_ba_params.solver_options)
+  if (a.force_general || w.info[INFO_MAX_DEGREE] > AM_DMAX) return;  // force_general: the walk + Schur pair takes every graph (vipe_ba_params.solver_options)
   const int k = blockIdx.y;
   const int beg = w.rowptr[k], end = w.rowptr[k + 1];
   if (beg == end) return;
@@ -372,7 +372,7 @@ __global__ __launch_bounds__(TILE) __attribute__((amdgpu_waves_per_eu(3, 3))) vo
   const int pose_i = k / V, qi = k % V;
   const int si = w.pose_slot[pose_i];
   const bool fi = si >= 0;
-  const int n_free = w.info[0], nrow = w.info[3];
+  const int n_free = w.info[INFO_FREE_POSES], nrow = w.info[INFO_UNKNOWNS];
   const int foff = 6 * n_free;
 
   // @astamp 0
@@ -522,7 +522,7 @@ __global__ __launch_bounds__(TILE) void ba_walk_kernel(BAArgs a) {
   constexpr int WBUF = 16 * AM_P1;
   const vipe_ba_params& prm = a.p;
   const BAWs& w = a.w;
-  if (!a.force_general && w.info[6] <= AM_DMAX) return;  // low-degree graphs: the fused kernel
+  if (!a.force_general && w.info[INFO_MAX_DEGREE] <= AM_DMAX) return;  // low-degree graphs: the fused kernel
   const int k = blockIdx.y;
   const int beg = w.rowptr[k], end = w.rowptr[k + 1];
   if (beg == end) return;
@@ -532,7 +532,7 @@ __global__ __launch_bounds__(TILE) void ba_walk_kernel(BAArgs a) {
   const bool dfree = flags & 2;
   const int pose_i = k / V, qi = k % V;
   const int si = w.pose_slot[pose_i];
-  const int n_free = w.info[0], nrow = w.info[3];
+  const int n_free = w.info[INFO_FREE_POSES], nrow = w.info[INFO_UNKNOWNS];
   const int foff = 6 * n_free;
 
   extern __shared__ __align__(16) float am_smem[];
@@ -615,7 +615,7 @@ __global__ __launch_bounds__(TILE) void ba_walk_rig_kernel(BAArgs a) {
   const bool dfree = flags & 2;
   const int pose_i = k / V, qi = k % V;
   const int si = w.pose_slot[pose_i];
-  const int n_free = w.info[0], nrow = w.info[3];
+  const int n_free = w.info[INFO_FREE_POSES], nrow = w.info[INFO_UNKNOWNS];
   const int foff = 6 * n_free, roff = foff + a.nintr;
   const bool oi = prm.optimize_intrinsics, orr = prm.optimize_rig_rotation;
 
@@ -823,7 +823,7 @@ constexpr int SC_GRID = 96;  // tile pairs processed in parallel per frame (the 
 template <int F>
 __global__ __launch_bounds__(TILE) void ba_schur_kernel(BAArgs a) {
   const BAWs& w = a.w;
-  if (!a.mv && !a.force_general && w.info[6] <= AM_DMAX) return;
+  if (!a.mv && !a.force_general && w.info[INFO_MAX_DEGREE] <= AM_DMAX) return;
   const int k = blockIdx.y;
   const int flags = w.fflags[k];
   const int beg = w.rowptr[k], end = w.rowptr[k + 1];
@@ -833,7 +833,7 @@ __global__ __launch_bounds__(TILE) void ba_schur_kernel(BAArgs a) {
   const int NR = 6 * (deg + 1) + NT + 1, RT = (NR + 15) >> 4, npairs = RT * (RT + 1) / 2;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, l16 = lane & 15, kq = lane >> 4;
   const int si = w.pose_slot[k / V];
-  const int n_free = w.info[0], nrow = w.info[3], foff = 6 * n_free;
+  const int n_free = w.info[INFO_FREE_POSES], nrow = w.info[INFO_UNKNOWNS], foff = 6 * n_free;
   __shared__ float tile[NWAVE][2][16 * AM_P2];
   __shared__ float red[NWAVE][256];
   __shared__ const float* rowp[32];

@@ -6,6 +6,20 @@ constexpr int NWAVE = TILE / WAVE;
 constexpr int TCHUNK = 8;   // terms whose transforms are staged in LDS at a time
 constexpr int AM_DMAX = 6;  // largest source-frame degree the matrix-core accumulate kernel handles
 
+// Slots of BAWs::info, copied to the caller's d_info (include/vipe_amd.h; ext/slam_ext.py reads two of them by number)
+enum InfoSlot {
+  INFO_FREE_POSES = 0,   // plan: free poses = 6x6 blocks of the reduced system
+  INFO_FREE_DISP = 1,    // plan: free disparity frames
+  INFO_FAILURES = 2,     // failed factorisations of this call (their step is zero)
+  INFO_UNKNOWNS = 3,     // plan: n = 6 free poses + tail unknowns
+  INFO_BAND_BLOCKS = 4,  // plan: band width of the pose part in 6x6 blocks
+  INFO_SOLVER = 5,       // a Solver: who solved the last iteration.  A report for the caller; no kernel reads it
+  INFO_MAX_DEGREE = 6,   // plan: largest number of terms of one source frame
+  INFO_TILED_FAIL = 7,   // tiled factorisation: a pivot of the current one failed (chol_potrf -> chol_backsub)
+};
+// Values of INFO_SOLVER; part of the ABI (vipe_ba_params.path_hint is learnt from them)
+enum Solver { SOLVER_GLOBAL = 0, SOLVER_BAND = 1, SOLVER_DENSE = 2 };
+
 struct BAWs {
   int* rowptr;      // [nF+1] CSR over source disparity frames
   int* order;       // [M] term ids sorted by source frame (stable)
@@ -13,7 +27,7 @@ struct BAWs {
   int* slot_pose;   // [nP] inverse map
   int* fflags;      // [nF] bit0 source, bit1 disparity free (the sensor-prior test is NOT part of the plan: finish_disp reads sens_sum, refreshed every call)
   int* scratch;     // [2*nP + nF]
-  int* info;        // [8] n_free, n_free_disp, chol_fail, n_unknowns
+  int* info;        // [8] by InfoSlot
   float* sens_sum;  // [nF]
   float* C;         // [nF,P] damped disparity diagonal
   float* wv;        // [nF,P]

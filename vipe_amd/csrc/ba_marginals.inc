@@ -17,10 +17,10 @@ __global__ void ba_term_slot_kernel(BAArgs a) {
   a.w.mslot[c] = ((int)a.pi[e] == pj) ? -1 : a.w.pose_slot[pj];
 }
 
-// the reduced system as the solvers see it: symmetric, LM damping on the diagonal (damped_diag), n = info[3] rows
+// the reduced system as the solvers see it: symmetric, LM damping on the diagonal (damped_diag), n = info[INFO_UNKNOWNS] rows
 __global__ void ba_export_reduced_kernel(BAArgs a, double* __restrict__ out, int ld_out) {
   const BAWs& w = a.w;
-  const int n = min(w.info[3], ld_out), npr = 6 * w.info[0];
+  const int n = min(w.info[INFO_UNKNOWNS], ld_out), npr = 6 * w.info[INFO_FREE_POSES];
   const int64_t nn = (int64_t)n * n;
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < nn; i += (int64_t)gridDim.x * blockDim.x) {
     const int r = (int)(i / n), c = (int)(i % n);
@@ -115,7 +115,7 @@ __global__ __launch_bounds__(TILE) void ba_disp_variance_kernel(BAArgs a, const 
   const int pc = min(p, P - 1);
   const int beg = w.rowptr[k], deg = w.rowptr[k + 1] - beg;
   const int si = w.pose_slot[k / a.p.n_views];
-  const int foff = 6 * w.info[0], n = min(w.info[3], ld);
+  const int foff = 6 * w.info[INFO_FREE_POSES], n = min(w.info[INFO_UNKNOWNS], ld);
   const int R = 6 * (deg + 1) + a.ntail, nch = (R + MG_CH - 1) / MG_CH;
   __shared__ MargLds sh;
 
@@ -157,7 +157,7 @@ __global__ void ba_marginals_finish_kernel(BAArgs a, const double* __restrict__ 
   for (int64_t i = gid; i < ns; i += nthr) w.S[i] = 0.0;
   for (int64_t i = gid; i < (int64_t)w.ld - 1; i += nthr) w.Hd[i] = 0.0;
   if (!Sinv || !pose_cov) return;
-  const int n = min(w.info[3], ld);
+  const int n = min(w.info[INFO_UNKNOWNS], ld);
   for (int64_t i = gid; i < (int64_t)a.p.n_poses * 36; i += nthr) {
     const int sl = w.pose_slot[i / 36], r = (int)(i % 36) / 6, c = (int)(i % 36) % 6;
     if (sl >= 0 && 6 * sl + 5 < n) pose_cov[i] = Sinv[(int64_t)(6 * sl + r) * ld + 6 * sl + c];

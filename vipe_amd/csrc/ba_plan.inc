@@ -5,8 +5,8 @@ __global__ __launch_bounds__(256) void ba_sens_kernel(const float* __restrict__ 
   // buffer.py:470-471: frames whose sensor disparity sums to > 0
   const int k = blockIdx.x;
   if (k == 0 && threadIdx.x == 0) {
-    info[2] = 0;  // Cholesky failure count of this call (also when the plan is reused)
-    info[5] = 0;  // "band solver solved": normally reset by that kernel itself, which a path hint may leave out
+    info[INFO_FAILURES] = 0;  // Cholesky failure count of this call (also when the plan is reused)
+    info[INFO_SOLVER] = SOLVER_GLOBAL;  // what a call in which nothing solved reports
   }
   float s = 0.f;
   for (int p = threadIdx.x; p < P; p += blockDim.x) s += sens[(int64_t)k * P + p];
@@ -110,12 +110,12 @@ __global__ __launch_bounds__(1024) void ba_plan_kernel(BAArgs a) {
     __syncthreads();
   }
   if (t == 0) {
-    a.w.info[0] = n_free;
-    a.w.info[1] = lds[0];
-    a.w.info[2] = 0;
-    a.w.info[3] = 6 * n_free + a.ntail;
-    a.w.info[4] = 0;  // band width of the reduced pose system in 6x6 blocks (filled below)
-    a.w.info[6] = 0;  // largest number of terms of one source frame (selects the accumulate kernel)
+    a.w.info[INFO_FREE_POSES] = n_free;
+    a.w.info[INFO_FREE_DISP] = lds[0];
+    a.w.info[INFO_FAILURES] = 0;
+    a.w.info[INFO_UNKNOWNS] = 6 * n_free + a.ntail;
+    a.w.info[INFO_BAND_BLOCKS] = 0;  // band width of the reduced pose system in 6x6 blocks (filled below)
+    a.w.info[INFO_MAX_DEGREE] = 0;  // largest number of terms of one source frame (selects the accumulate kernel)
   }
   // stable counting sort of the terms by source frame: frame k's owner scans the term list in order
   // (cursor kept in cnt[]: reuse cnt as the running write position)
@@ -146,7 +146,7 @@ __global__ __launch_bounds__(1024) void ba_plan_kernel(BAArgs a) {
       const int sj = a.w.pose_slot[(int)a.pj[a.w.order[q]]];
       if (sj >= 0) { lo = min(lo, sj); hi = max(hi, sj); }
     }
-    if (hi >= 0) atomicMax(&a.w.info[4], hi - lo);
-    atomicMax(&a.w.info[6], a.w.rowptr[k + 1] - a.w.rowptr[k]);
+    if (hi >= 0) atomicMax(&a.w.info[INFO_BAND_BLOCKS], hi - lo);
+    atomicMax(&a.w.info[INFO_MAX_DEGREE], a.w.rowptr[k + 1] - a.w.rowptr[k]);
   }
 }

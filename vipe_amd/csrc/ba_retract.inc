@@ -31,7 +31,7 @@ __global__ __launch_bounds__(TILE) void ba_retract_kernel(BAArgs a) {
   const int beg = w.rowptr[k], end = w.rowptr[k + 1];
   float rhs = w.wv[kp];
   const int si = w.pose_slot[k / V];
-  const int n_free = w.info[0];
+  const int n_free = w.info[INFO_FREE_POSES];
   // DROID leaves pose slot 0 out of the back-substitution (EvT6x1_kernel: idx <= 0 returns, geom_kernels.cu:1085)
   const int smin = a.droid ? 1 : 0;
   if (si >= smin) {

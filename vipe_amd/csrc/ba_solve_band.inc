@@ -11,12 +11,11 @@
 // entries of the NEXT diagonal block - already factors that block (look-ahead), barrier.  The back substitution is
 // run by wave 0 alone: 8 lanes per column, DPP reductions, the 6x6 triangular solve replicated in every lane with
 // stored reciprocal pivots - no workgroup barrier and no division on the dependent chain.
-// Sets info[5] = 1 when it solved the system (the global-memory kernel launched after it then exits).
+// Takes the systems band_form (ba_route.cuh) gives it, in the form it names, and reports SOLVER_BAND in info[INFO_SOLVER].
 //
 // The pieces of a block step are written once, over one LDS band image (BandImage), and called by the one-chain body
 // (one image) and the two-chain body (one image per chain).  The workgroup barriers are the bodies', not the pieces'.
-constexpr int BAND_T = 512;  // threads per image
-constexpr int BAND_UPT = 6;  // trailing-update pairs per thread: dense 12-pose windows (PB = 66: 2277 pairs) still fit
+// (BAND_T threads per image, BAND_UPT, band_npair and the LDS sizes of the carves: ba_route.cuh)
 
 struct BandImage {
   double* L;      // band rows [npr][WBP]; the offsets below and in BandPairs count doubles from here
@@ -30,12 +29,6 @@ struct BandImage {
 };
 
 __device__ __forceinline__ int band_ofs(const BandImage& b, int r, int c) { return r * b.WBP + c - 6 * (r / 6) + b.PB; }
-
-// trailing-update pairs of a block step: pose-pose (lower triangle of the PB rows below the block), tail-pose, tail-tail
-__device__ __forceinline__ int band_npair(int PB, int ntail) {
-  const int F = ntail - 1;
-  return PB * (PB + 1) / 2 + ntail * PB + (F == 0 ? 0 : (F == 1 ? 2 : 5));
-}
 
 // 6x6 diagonal block of pose kb: factor in registers, publish L (band), blk, rd, rdall
 __device__ __forceinline__ void band_factor_diag(const BandImage& b, int kb) {
@@ -276,24 +269,21 @@ __device__ __forceinline__ void band_backsub_block(const BandImage& b, int tl, i
 // Short neighbourhood graphs and those with intrinsics columns run the <2, false> instantiation (fewer slots to walk per
 // step, one pipelined load pass); the frontend's dense windows the <BAND_UPT, true> one.
 template <int UPT, bool TWO>
-__device__ __forceinline__ void band_solve_body(const BAArgs& a, int lds_doubles, unsigned char* smem_raw) {
+__device__ __forceinline__ void band_solve_body(const BAArgs& a, const RouteIn& r, unsigned char* smem_raw) {
   const int t = threadIdx.x;
   double* const L = reinterpret_cast<double*>(smem_raw);
   const BAWs& w = a.w;
-  const int n = w.info[3], n_free = w.info[0], bandblk = w.info[4];
+  const int n = r.n, n_free = r.n_free, bandblk = r.bandblk;
   const int ld = w.ld;
   const int npr = 6 * n_free, ntail = n - npr + 1;  // tail rows: intrinsics rows, then the rhs row
   const int F = ntail - 1;
   const int PB = 6 * bandblk, WB = PB + 6, WBP = WB + 1;
-  // LDS carve: band [npr][WBP], tail [ntail][n + 1], rdall [npr], blk[6][7], rd[6], flags
-  const int TL0 = npr * WBP;
-  const int RD0 = TL0 + ntail * (n + 1);
-  const int need = RD0 + npr + 64;
-  if (t == 0) w.info[5] = 0;
-  if (n == 0 || need > lds_doubles || band_npair(PB, ntail) > 21 + UPT * (BAND_T - 64) || PB + ntail > BAND_T ||
-      WBP > (TWO ? 128 : 64) || F > 2) {
-    return;
-  }
+  // band_form let the system in, so its limits hold; the optimiser does not see that through the form's value, and
+  // this one shapes the tail loops below
+  __builtin_assume(F <= LDS_TAIL_MAX);
+  // LDS carve: band [npr][WBP], tail [ntail][n + 1], rdall [npr], blk[6][7], rd[6], flags (band_need doubles)
+  const int TL0 = band_tail0(npr, WBP);
+  const int RD0 = band_rd0(n, npr, ntail, WBP);
   double* const Tl = L + TL0;
   BandImage b;
   b.L = L; b.tl0 = TL0; b.tp = n + 1; b.y = Tl + F * (n + 1);
@@ -369,8 +359,8 @@ __device__ __forceinline__ void band_solve_body(const BAArgs& a, int lds_doubles
   __syncthreads();
   const bool bad = *b.failp != 0;
   if (t == 0) {
-    if (bad) w.info[2] += 1;
-    w.info[5] = 1;
+    if (bad) w.info[INFO_FAILURES] += 1;
+    w.info[INFO_SOLVER] = SOLVER_BAND;
   }
   for (int dd = t; dd < n; dd += BAND_T) store_step(w, dd, y[dd], bad);
   __syncthreads();
@@ -388,25 +378,20 @@ __device__ __forceinline__ void band_solve_body(const BAArgs& a, int lds_doubles
 // runs separator first, then both chains at once.  Dependent block steps: max(a, b) + bandblk forward,
 // bandblk + max(a, b) back, instead of nb + nb.
 // The kernel is launched with 2 * BAND_T threads: BAND_T per chain; the one-chain forms use the first BAND_T.
-__device__ __forceinline__ bool band2_solve_body(const BAArgs& a, int lds_doubles, unsigned char* smem_raw) {
+__device__ __forceinline__ void band2_solve_body(const BAArgs& a, const RouteIn& r, unsigned char* smem_raw) {
   const BAWs& w = a.w;
   // image B's threads are rotated by one wave: its critical wave (tl < 64: diagonal pairs, look-ahead factor, back
   // substitution) is then hardware wave 9 - another SIMD than image A's wave 0 (waves go to SIMDs round robin); with both
   // chains' critical waves on one SIMD each ran at the pace of two
   const int t = threadIdx.x, g = t >= BAND_T ? 1 : 0, tl = g ? ((t - 64) & (BAND_T - 1)) : t;
-  const int n = w.info[3], nb = w.info[0], bandblk = w.info[4];
+  const int n = r.n, nb = r.n_free, bandblk = r.bandblk;
   const int ld = w.ld;
-  if (n != 6 * nb || bandblk < 1 || nb < 4 * bandblk + 4) return false;
   const int PB = 6 * bandblk, WB = PB + 6, WBP = WB + 1;
-  if (PB + 7 > 64) return false;
   const int ca = (nb - bandblk) / 2, cb = nb - bandblk - ca;  // chain lengths in blocks (cb >= ca)
   const int nf = (g ? cb : ca) + bandblk, chain = g ? cb : ca;  // blocks of this image, of its chain
-  const int nfmax = cb + bandblk;
-  const int npr = 6 * nf, nprmax = 6 * nfmax;
-  if (band_npair(PB, 1) > 21 + 2 * (BAND_T - 64)) return false;
+  const int npr = 6 * nf, nprmax = band2_rows_max(nb, bandblk);  // 6 (cb + bandblk)
   // LDS carve per image: band [nprmax][WBP], rhs row [nprmax + 1], rdall [nprmax], blk 42, rd 6; then one flag
-  const int IMG = nprmax * WBP + (nprmax + 1) + nprmax + 48;
-  if (2 * IMG + 8 > lds_doubles) return false;
+  const int IMG = band2_image(nprmax, WBP);
   double* const LA = reinterpret_cast<double*>(smem_raw);
   double* const LB = LA + IMG;
   BandImage b;
@@ -423,7 +408,7 @@ __device__ __forceinline__ bool band2_solve_body(const BAArgs& a, int lds_double
   auto gblk = [&](int l) { return g ? nb - 1 - l : l; };  // local block -> global block
   // @bstamp 0
   // @bwave 100
-  if (t == 0) { *b.failp = 0; w.info[5] = 0; }
+  if (t == 0) *b.failp = 0;
 
   // ---- load both images.  Image B: mirrored; its separator square and separator right-hand side start from zero (they
   // only collect chain B's contributions)
@@ -541,28 +526,24 @@ __device__ __forceinline__ bool band2_solve_body(const BAArgs& a, int lds_double
   // @bstamp 6
   const bool bad = *b.failp != 0;
   if (t == 0) {
-    if (bad) w.info[2] += 1;
-    w.info[5] = 1;
+    if (bad) w.info[INFO_FAILURES] += 1;
+    w.info[INFO_SOLVER] = SOLVER_BAND;
   }
   // image A: chain + separator, image B: its chain
   for (int r = tl; r < (g ? 6 * cb : npr); r += BAND_T) store_step(w, 6 * gblk(r / 6) + r % 6, y[r], bad);
   __syncthreads();
   apply_retraction(a, t, 2 * BAND_T, nb);
   // @bstamp 7
-  return true;
 }
 
 __global__ __launch_bounds__(2 * BAND_T) void ba_solve_band_kernel(BAArgs a, int lds_doubles) {
   extern __shared__ __align__(16) unsigned char smem_raw[];
-  const BAWs& w = a.w;
-  const int n = w.info[3], n_free = w.info[0], bandblk = w.info[4];
-  const int ntail = n - 6 * n_free + 1, F = ntail - 1;
-  const int PB = 6 * bandblk;
-  const bool wide = PB + 7 > 64 || band_npair(PB, ntail) > 21 + 2 * (BAND_T - 64);
-  // long pose-only chains: both ends at once, one chain per half of the workgroup (a uniform decision made before any
-  // barrier; the caller's VIPE_BA_OPT_ONE_CHAIN keeps the one-chain form for A/B - BAArgs::band2)
-  if (!wide && F == 0 && a.band2 && band2_solve_body(a, lds_doubles, smem_raw)) return;
-  if (threadIdx.x >= BAND_T) return;  // the one-chain forms are written for BAND_T threads
-  if (wide) band_solve_body<BAND_UPT, true>(a, lds_doubles, smem_raw);
-  else band_solve_body<2, false>(a, lds_doubles, smem_raw);
+  // a uniform decision made before any barrier (the caller's VIPE_BA_OPT_ONE_CHAIN keeps the one-chain forms for A/B -
+  // BAArgs::band2)
+  const RouteIn r = route_in(a, lds_doubles);
+  const int form = band_form(r);
+  if (form == BAND_TWO_CHAIN) { band2_solve_body(a, r, smem_raw); return; }
+  if (form == BAND_DECLINES || threadIdx.x >= BAND_T) return;  // the one-chain forms are written for BAND_T threads
+  if (form == BAND_WIDE) band_solve_body<BAND_UPT, true>(a, r, smem_raw);
+  else band_solve_body<2, false>(a, r, smem_raw);
 }

@@ -18,11 +18,8 @@
 // A single wave issues at most one instruction every ~4 cycles and a dependent fp64 operation takes ~35: the phases were
 // sized by in-kernel cycle stamps (scratch/make_ba_stamps.py) - before this form the chain (2 850 cycles per block) ran
 // in sequence with the panel, the update and the extraction (7 700 per step).
-// Sets info[5] = 2 when it solved the system.
-constexpr int DN_T = 512;
-constexpr int DN_PP = 20;     // panel buffer: doubles per row = 2 parities x 8 + 4 (20 l16 mod 32 takes 8 values 4 apart: with kq the 64
-                              // lanes of an operand-fragment read cover the 32 8-byte slots of the bank window twice - a pitch of 16 is 8-way conflicted)
-constexpr int DN_SLOTS = 10;  // 6 tile waves x 10 >= 55 tiles (n + 1 <= 160 rows: 10 tile rows; 11 slots spill)
+// Takes the systems dense_takes (ba_route.cuh, with DN_T, DN_PP, DN_SLOTS and the LDS sizes) gives it and reports
+// SOLVER_DENSE in info[INFO_SOLVER].
 typedef double double4c __attribute__((ext_vector_type(4)));
 
 __global__ __launch_bounds__(DN_T) void ba_solve_dense_kernel(BAArgs a, int lds_doubles) {
@@ -30,14 +27,11 @@ __global__ __launch_bounds__(DN_T) void ba_solve_dense_kernel(BAArgs a, int lds_
   double* const L = reinterpret_cast<double*>(smem_raw);
   const BAWs& w = a.w;
   const int t = threadIdx.x;
-  const int n = w.info[3], n_free = w.info[0];
+  if (!dense_takes(route_in(a, lds_doubles))) return;
+  const int n = w.info[INFO_UNKNOWNS], n_free = w.info[INFO_FREE_POSES];
   const int npr = 6 * n_free, F = n - npr;
-  const int NP = ((n + 1) * (n + 2) / 2 + 1) & ~1;  // packed size incl. the rhs row (even: what follows is 16-byte aligned)
-  const int NTR = (n + 16) >> 4, NTL = NTR * (NTR + 1) / 2;  // tile rows covering rows 0..n; tiles of the triangle
-  const int LDS_NEED = NP + 64 + 2 * 36 + 36 + (n + 8) + 6 * (n + 6) + DN_PP * 16 * NTR;
-  // info[5] == 1: the band solver (which resets the flag whenever it runs) solved THIS iteration.  A 2 can only be this
-  // kernel's own mark from the previous Gauss-Newton iteration of the call (ba_sens_kernel clears the flag per call).
-  if (n == 0 || w.info[5] == 1 || a.mv || LDS_NEED > lds_doubles || F > 2 || NTL > 6 * DN_SLOTS) return;
+  const int NP = dense_packed(n);  // packed size incl. the rhs row
+  const int NTR = dense_tile_rows(n), NTL = dense_tiles(n);  // tile rows covering rows 0..n; tiles of the triangle
   double* const blk = L + NP;      // 6x7: the current diagonal factor block
   double* const rd = blk + 42;     // its reciprocal pivots
   int* const failp = reinterpret_cast<int*>(rd + 6);
@@ -471,8 +465,8 @@ __global__ __launch_bounds__(DN_T) void ba_solve_dense_kernel(BAArgs a, int lds_
       }
     }
     if (t == 0) {
-      if (bad) w.info[2] += 1;
-      w.info[5] = 2;
+      if (bad) w.info[INFO_FAILURES] += 1;
+      w.info[INFO_SOLVER] = SOLVER_DENSE;
     }
   }
   // @stamp 4

@@ -1,17 +1,20 @@
 // ------------------------------------------------------------------------------------------------ solve
 
-// Dense Cholesky solve of the reduced system by ONE workgroup (16 waves), fp64.
+// Cholesky solve of the reduced system in global memory by ONE workgroup of 8 waves, fp64: the systems of up to
+// CT_MIN_N unknowns that neither LDS solver takes (global_form, ba_route.cuh; multi-view rigs among them).
 //   S: lower triangle, row-major, ld; row n holds the rhs, so the forward substitution y = L^-1 g falls out of
-//   the factorisation as the last panel row.  Right-looking, NB = 24 columns per step:
-//     1. diagonal block: wave 0, one matrix row per lane in registers, column-by-column (Crout) with the
-//        finished columns published to LDS;
-//     2. panel: one row per thread, X Lkk^T = A by forward substitution against Lkk in LDS; the solved panel is
-//        kept TRANSPOSED in LDS (PT[j][row]) so the update below reads it without bank conflicts;
-//     3. trailing update A22 -= P P^T: 1x4 register tiles per thread, panel from LDS, S read-modify-write in
-//        32-byte row segments.
-//   Then blocked backward substitution L^T x = y and the pose / intrinsics retraction.
+//   the factorisation as the last panel row.  Right-looking, NB = 12 columns per step:
+//     1. diagonal block: wave 0, one matrix row per lane in registers, column by column with the finished columns
+//        published to LDS;
+//     2. panel: one row per thread - only the rows that can be nonzero in these columns, i.e. the pose rows inside
+//        the band and the dense tail rows - X Lkk^T = A by forward substitution against Lkk in LDS; the solved panel
+//        is also kept TRANSPOSED in LDS (PT[j][panel row]), where the update reads its operands;
+//     3. trailing update A22 -= P P^T on the fp64 matrix cores: 16 x 16 tiles of the panel rows' lower triangle, one
+//        tile per wave at a time, S read-modify-write.
+//   Then the diagonal blocks are inverted in place (upper triangle of S, Hd), the backward substitution L^T x = y
+//   runs block by block, and the poses / intrinsics / rig are retracted.  Reports SOLVER_GLOBAL in info[INFO_SOLVER].
+// The panel always fits its LDS buffer: n <= CT_MIN_N here, and run_iters (ba.hip) checks CT_MIN_N + 1 <= panel_cap.
 constexpr int NB = 12;
-constexpr int CT_MIN_N = 256;  // larger systems take the tiled, chip-wide factorisation further down
 constexpr int SOLVE_T = 512;  // 8 waves: up to 256 VGPRs per lane, no spills in the register-resident phases
 
 struct SolveLds {
@@ -27,21 +30,19 @@ __global__ __launch_bounds__(SOLVE_T) void ba_solve_kernel(BAArgs a, int panel_c
   double* PT = reinterpret_cast<double*>(smem_raw + ((sizeof(SolveLds) + 15) / 16) * 16);  // [NB][panel_cap]
   const BAWs& w = a.w;
   const int t = threadIdx.x;
-  const int n = w.info[3], n_free = w.info[0];
+  const int n = w.info[INFO_UNKNOWNS], n_free = w.info[INFO_FREE_POSES];
   const int ld = w.ld;
   double* S = w.S;
   if (t == 0) sh.fail = 0;
-  if (n == 0 || w.info[5] != 0 || n > CT_MIN_N) return;  // an LDS solver (band: 1, dense: 2) took the system; large ones: tiled
+  if (global_form(route_in(a)) != GLOBAL_ONE_WORKGROUP) return;
   // LM damping on the diagonal
   for (int dd = t; dd < n; dd += SOLVE_T) {
     double& sdd = S[(int64_t)dd * ld + dd];
     sdd = damped_diag(a, dd, 6 * n_free, sdd, a.droid ? 0.0 : w.Hd[dd]);
   }
   __syncthreads();
-  const bool use_lds_panel = (n + 1) <= panel_cap;
   const int npose_rows = 6 * n_free;
-  // band of the pose part in 6x6 blocks (plan kernel); the scalar fallback path treats the system as dense
-  const int bandblk = use_lds_panel ? w.info[4] : n;
+  const int bandblk = w.info[INFO_BAND_BLOCKS];  // band of the pose part in 6x6 blocks (plan kernel)
 
   for (int k0 = 0; k0 < n; k0 += NB) {
     const int bw = min(NB, n - k0);
@@ -114,14 +115,14 @@ __global__ __launch_bounds__(SOLVE_T) void ba_solve_kernel(BAArgs a, int panel_c
 #pragma unroll
       for (int j = 0; j < NB; ++j) {
         if (j < bw) grow[j] = x[j];
-        if (use_lds_panel) PT[j * panel_cap + pr] = j < bw ? x[j] : 0.0;
+        PT[j * panel_cap + pr] = j < bw ? x[j] : 0.0;
       }
     }
     __syncthreads();
     // ---- 3. trailing update A22 -= P P^T on the fp64 matrix cores (v_mfma_f64_16x16x4_f64): 16x16 tiles of the
-    //         lower triangle, one tile per wave at a time, K = 24 = 6 MFMAs; operands straight from the
+    //         lower triangle, one tile per wave at a time, K = NB = 3 MFMAs; operands straight from the
     //         transposed panel in LDS (lane l: A[row l&15][k l>>4], B[k l>>4][col l&15]).
-    if (use_lds_panel) {
+    {
       typedef double double4v __attribute__((ext_vector_type(4)));
       const int wv = t >> 6, ln = t & 63;
       const int nt = (m + 15) >> 4;
@@ -142,36 +143,6 @@ __global__ __launch_bounds__(SOLVE_T) void ba_solve_kernel(BAArgs a, int panel_c
         for (int r4 = 0; r4 < 4; ++r4) {
           const int rr = 16 * ti + (ln >> 4) + 4 * r4;
           if (rr < m && cc <= rr && cc <= m - 2) S[(int64_t)prow(rr) * ld + prow(cc)] -= c[r4];
-        }
-      }
-    } else {
-      const int tx = t & 31, ty = t >> 5;  // 32 x 32 threads, each a 1 x 4 tile
-      for (int rr = ty; rr < m; rr += SOLVE_T / 32) {
-        const int cmax = min(rr, m - 2);  // inclusive
-        for (int c4 = tx * 4; c4 <= cmax; c4 += 128) {
-          double acc0 = 0, acc1 = 0, acc2 = 0, acc3 = 0;
-          if (use_lds_panel) {
-#pragma unroll 4
-            for (int j = 0; j < bw; ++j) {
-              const double pr_ = PT[j * panel_cap + rr];
-              const double* pc = PT + j * panel_cap + c4;
-              acc0 += pr_ * pc[0]; acc1 += pr_ * pc[1]; acc2 += pr_ * pc[2]; acc3 += pr_ * pc[3];
-            }
-          } else {
-            const double* prw = S + (int64_t)(r0 + rr) * ld + k0;
-            for (int j = 0; j < bw; ++j) {
-              const double pr_ = prw[j];
-              acc0 += pr_ * S[(int64_t)(r0 + c4) * ld + k0 + j];
-              if (c4 + 1 <= cmax) acc1 += pr_ * S[(int64_t)(r0 + c4 + 1) * ld + k0 + j];
-              if (c4 + 2 <= cmax) acc2 += pr_ * S[(int64_t)(r0 + c4 + 2) * ld + k0 + j];
-              if (c4 + 3 <= cmax) acc3 += pr_ * S[(int64_t)(r0 + c4 + 3) * ld + k0 + j];
-            }
-          }
-          double* dst = S + (int64_t)(r0 + rr) * ld + r0 + c4;
-          dst[0] -= acc0;
-          if (c4 + 1 <= cmax) dst[1] -= acc1;
-          if (c4 + 2 <= cmax) dst[2] -= acc2;
-          if (c4 + 3 <= cmax) dst[3] -= acc3;
         }
       }
     }
@@ -212,7 +183,7 @@ __global__ __launch_bounds__(SOLVE_T) void ba_solve_kernel(BAArgs a, int panel_c
     }
   }
   __syncthreads();
-  // (ii) blocks from the last to the first: x_k = Lkk^-T y_k (a 24x24 mat-vec, lane j: sum_m Linv[m][j] y[m]),
+  // (ii) blocks from the last to the first: x_k = Lkk^-T y_k (an NB x NB mat-vec, lane j: sum_m Linv[m][j] y[m]),
   //      then y_c -= sum_m L[k0+m][c] x_k[m] for every earlier column c (coalesced row reads).
   double* yrow = S + (int64_t)n * ld;
   for (int k0 = ((n - 1) / NB) * NB; k0 >= 0; k0 -= NB) {
@@ -246,7 +217,10 @@ __global__ __launch_bounds__(SOLVE_T) void ba_solve_kernel(BAArgs a, int panel_c
     __syncthreads();
   }
   const bool bad = sh.fail != 0;
-  if (t == 0 && bad) w.info[2] += 1;
+  if (t == 0) {
+    if (bad) w.info[INFO_FAILURES] += 1;
+    w.info[INFO_SOLVER] = SOLVER_GLOBAL;
+  }
   for (int dd = t; dd < n; dd += SOLVE_T) store_step(w, dd, yrow[dd], bad);
   __syncthreads();
   apply_retraction(a, t, SOLVE_T, n_free);
@@ -282,8 +256,8 @@ __device__ __forceinline__ double rsqrt_seeded(double x) {
 }
 
 __device__ __forceinline__ bool chol_active(const BAArgs& a, int& n) {
-  n = a.w.info[3];
-  return n > CT_MIN_N && a.w.info[5] == 0;
+  n = a.w.info[INFO_UNKNOWNS];
+  return global_form(route_in(a)) == GLOBAL_TILED;
 }
 
 __global__ __launch_bounds__(256) void chol_potrf_kernel(BAArgs a, int k) {
@@ -299,7 +273,7 @@ __global__ __launch_bounds__(256) void chol_potrf_kernel(BAArgs a, int k) {
   __shared__ double Li[CT][CT + 1];   // its inverse (lower)
   __shared__ int fail;
   if (t == 0) fail = 0;
-  if (k == 0 && t == 0) w.info[7] = 0;  // failure flag of this factorisation
+  if (k == 0 && t == 0) w.info[INFO_TILED_FAIL] = 0;  // failure flag of this factorisation
   __syncthreads();
   // the tile travels global <-> LDS with all 256 threads (row segments, coalesced), LM damping (damped_diag) added on the
   // way in.  The last tile column of a system with
@@ -307,7 +281,7 @@ __global__ __launch_bounds__(256) void chol_potrf_kernel(BAArgs a, int k) {
   // factorisation as one more row below the diagonal (its own "diagonal" entry is a dummy 1).
   const bool has_rhs = bw < CT && c0 + bw == n;
   {
-    const int n_free = w.info[0];
+    const int n_free = w.info[INFO_FREE_POSES];
     double v[16], hd[16];  // all loads of the thread in flight before the first LDS store
 #pragma unroll
     for (int q = 0; q < 16; ++q) {
@@ -457,7 +431,7 @@ __global__ __launch_bounds__(256) void chol_potrf_kernel(BAArgs a, int k) {
   }
   double* Wk = w.Wi + (int64_t)k * CT * CT;
   for (int i = t; i < CT * CT; i += 256) Wk[i] = Li[i >> 6][i & 63];
-  if (t == 0 && fail) w.info[7] = 1;
+  if (t == 0 && fail) w.info[INFO_TILED_FAIL] = 1;
 }
 
 // X = A L^-T for the tile rows below tile k; grid = tile rows (exits beyond the matrix)
@@ -567,7 +541,7 @@ __global__ __launch_bounds__(512) void chol_backsub_kernel(BAArgs a) {
   int n;
   if (!chol_active(a, n)) return;
   const BAWs& w = a.w;
-  const int ld = w.ld, t = threadIdx.x, n_free = w.info[0];
+  const int ld = w.ld, t = threadIdx.x, n_free = w.info[INFO_FREE_POSES];
   __shared__ double Li[2][CT][CT + 1];
   __shared__ double xk[CT];
   extern __shared__ __align__(16) double ys[];  // [n]: the running right-hand side stays in LDS
@@ -620,8 +594,11 @@ __global__ __launch_bounds__(512) void chol_backsub_kernel(BAArgs a) {
     }
     __syncthreads();
   }
-  const bool bad = w.info[7] != 0;
-  if (t == 0 && bad) w.info[2] += 1;
+  const bool bad = w.info[INFO_TILED_FAIL] != 0;
+  if (t == 0) {
+    if (bad) w.info[INFO_FAILURES] += 1;
+    w.info[INFO_SOLVER] = SOLVER_GLOBAL;
+  }
   for (int dd = t; dd < n; dd += 512) store_step(w, dd, ys[dd], bad);
   __syncthreads();
   apply_retraction(a, t, 512, n_free);

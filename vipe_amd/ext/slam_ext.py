@@ -248,6 +248,13 @@ def dense_ba_marginals(*args, **kwargs):
     return disp_var, pose_cov, info
 
 
+# The two d_info slots read here, the solver ids and the degree limit: enum InfoSlot, enum Solver and AM_DMAX in
+# csrc/ba_common.cuh
+INFO_SOLVER, INFO_MAX_DEGREE = 5, 6
+SOLVER_GLOBAL, SOLVER_BAND, SOLVER_DENSE = 0, 1, 2
+AM_DMAX = 6  # the matrix-core accumulate kernel covers source-frame degrees up to this
+
+
 def _path_hint(state, key):
     """vipe_ba_params.path_hint for the plan `key` of this caller, or 0 while nothing has been learnt about it yet."""
     if key is None or not PLAN_REUSE:
@@ -261,9 +268,9 @@ def _path_hint(state, key):
         del state["pending"]
         if len(hints) > 64:
             hints.clear()
-        degree, solved = int(host[6]), int(host[5])  # solved: 0 global-memory Cholesky, 1 LDS band solver, 2 LDS dense solver
-        if degree > 0:  # AM_DMAX = 6 in csrc/ba_common.cuh: the matrix-core accumulate kernel covers source degrees up to 6
-            hints[k] = (1 if degree <= 6 else 2) | {0: 8 | 16, 1: 4 | 16, 2: 4 | 8}.get(solved, 0)
+        degree, solved = int(host[INFO_MAX_DEGREE]), int(host[INFO_SOLVER])
+        if degree > 0:
+            hints[k] = (1 if degree <= AM_DMAX else 2) | {SOLVER_GLOBAL: 8 | 16, SOLVER_BAND: 4 | 16, SOLVER_DENSE: 4 | 8}.get(solved, 0)
     return hints.get(key, 0)
 
 
