@@ -85,7 +85,8 @@ int vipe_corr_pyramid_lookup_nhwc(const void* const* h_levels, const float* d_co
 
 /* [fused] 4-level radius-3 lookup (droid_net.py:71-82) + the correlation encoder's first layer, Conv2d(196, Cout, 1)
  * + bias + activation (droid_net.py:436-437, 481): out[B,h1,w1,out_ctot] channels [out_coff, out_coff+Cout) fp16.
- * d_w_packed / d_bias as produced by vipe_conv_pack_weights for a [Cout, 200, 1, 1] weight (196 + 4 zero inputs).
+ * d_w_packed / d_bias as produced by vipe_conv_pack_weights for a [Cout, 200, 1, 1] weight (196 + 4 zero inputs); d_bias
+ * readable up to the padded output-channel count of vipe_conv_packed_dims, values behind Cout ignored.
  * fp16 volume levels, Cout == 128; other configurations return VIPE_EUNSUPPORTED (use lookup_nhwc + conv2d).
  * d_slots (optional, [B] int32): edge b reads slot d_slots[b] of the level buffers (a pool of pyramids with capacity
  * >= B whose edges come and go without compaction, factor_graph.py:147-152,194-196); null: slot b.
@@ -447,7 +448,10 @@ int vipe_ms_deform_attn_backward(const void* d_value, const int64_t* d_spatial_s
  * [fused] flow-update operator convolutions (UpdateModule, droid_net.py:432-499): NHWC fp16
  * implicit-GEMM convolution on MFMA, fp32 accumulate, fused bias + activation.
  *   x [B,H,W,Cin_total] f16, reads channels [cin_off, cin_off+Cin); w packed [KH*KW, Cin, Cout] f16
- *   (vipe_conv_pack_weights from the OIHW checkpoint layout); bias [Cout] f32;
+ *   (vipe_conv_pack_weights from the OIHW checkpoint layout); bias [Cout] f32 in a buffer that is READABLE up to
+ *   cout_pad floats (vipe_conv_packed_dims): the tile kernels load the bias in the vectors of their padded channel tile;
+ *   the values behind Cout are ignored (any bit pattern), only the memory has to exist.  This holds for d_bias of
+ *   vipe_conv2d_nhwc_f16, vipe_conv2d_fused and vipe_corr_lookup_conv1x1;
  *   y [B,H,W,Cout_total] f16, writes channels [cout_off, cout_off+Cout).
  *   act: 0 none, 1 relu, 2 sigmoid, 3 tanh.  Stride 1, "same" padding.
  *   extra [B,Cout] f32 (optional, NULL = none): per-image additive term (the *_glo 1x1 of the GRU).
@@ -496,7 +500,8 @@ int vipe_conv2d_fused(const void* d_x0, int x0_ctot, int x0_coff, const void* d_
 /* [fused] the whole flow-update operator (UpdateModule.forward, droid_net.py:467-499) sequenced natively: the 13 fused
  * convolutions above + vipe_corr_lookup_conv1x1 + vipe_segment_mean_nhwc_f16 + the pooled-context product in ONE call
  * (issued one by one from the host each launch costs more than most of them run for on a frontend window).
- * All tensors channels-last fp16 unless noted; the weight descriptors are `vipe_conv_pack_weights` outputs + fp32 biases. */
+ * All tensors channels-last fp16 unless noted; the weight descriptors are `vipe_conv_pack_weights` outputs + fp32 biases
+ * (each readable up to its convolution's padded output-channel count, see d_bias above). */
 typedef struct {
   const void *corr0_w, *corr2_w, *flow0_w, *flow2_w, *gw_w, *zr_w, *q_w, *zr_s_w, *q_s_w, *heads0_w, *heads2_w, *agg2_w, *eta_w;
   const void *zr_n_w, *zr_x_w; /* z|r gate weights over the hidden state only [256 <- 128] and over (corr | flow) only

@@ -285,7 +285,8 @@ def corr_lookup_conv1x1(levels, coords, w_packed, bias, out, out_coff=0, cout=12
     (droid_net.py:436-437): writes out[E,h,w,C] channels [out_coff, out_coff + cout) without materialising the
     196-channel lookup.  levels: fp16 pyramid of `corr_pyramid_build` (reference layout) or of
     `corr_pyramid_build_indexed` (blocked layout: 7-D level 0; `grid` = (h, w) of the targets, needed when the store is
-    padded); coords [E,h,w,2] f32.
+    padded); coords [E,h,w,2] f32.  w_packed / bias: the buffers of an `update_engine._Packed` (the bias readable up to
+    the padded output-channel count, as the header asks).
     Raises NotImplementedError for configurations the fused kernel does not cover (callers fall back to
     `corr_pyramid_lookup_nhwc` + the conv)."""
     check_gpu_contig(coords, out, *levels)

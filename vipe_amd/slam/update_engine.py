@@ -38,7 +38,8 @@ CORR_CH = 200  # 196 correlation channels padded to a multiple of 8 (zeros)
 
 
 class _Packed:
-    """Weights of one (possibly fused) convolution packed for conv_mfma: [K_pad/64][Cout_pad][64] fp16."""
+    """Weights of one (possibly fused) convolution packed for conv_mfma: [K_pad/64][Cout_pad][64] fp16, and its bias as
+    the [Cout_pad] float32 buffer the convolution entry points ask for (`bias` [Cout], zeros behind it)."""
 
     def __init__(self, w_oihw, bias, device):
         w = w_oihw.detach().to(device=device, dtype=torch.float16).contiguous()
@@ -49,7 +50,10 @@ class _Packed:
         self.packed = torch.empty(kp.value * cp.value, dtype=torch.float16, device=device)
         check(lib().vipe_conv_pack_weights(ptr(w), ptr(self.packed), self.cout, self.cin, self.kh, self.kw, 0,
                                            stream_ptr(w)), "conv_pack_weights")
-        self.bias = bias.detach().to(device=device, dtype=torch.float32).contiguous()
+        # the kernels read the bias up to the padded output-channel count (include/vipe_amd.h): [Cout_pad] with a zero tail
+        assert bias.numel() == self.cout, (tuple(bias.shape), self.cout)
+        self.bias = torch.zeros(cp.value, dtype=torch.float32, device=device)
+        self.bias[:self.cout] = bias.detach().to(device=device, dtype=torch.float32).reshape(-1)
         self.flops_per_pixel = 2.0 * self.cout * self.cin * self.kh * self.kw
 
 
