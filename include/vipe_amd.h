@@ -683,6 +683,79 @@ int vipe_frame_ingest(const void* d_rgb, int rgb_dtype, const unsigned char* d_m
 int vipe_convex_upsample(const void* d_mask, int mask_dtype, const float* d_data, float* d_out, const int64_t* d_rows,
                          int N, int R, int h, int w, int C, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Sparse keypoint tracker: corner detection and pyramidal Lucas-Kanade (klt_track.hip), the producer of the tracks
+ * that `SparseTracks` feeds to the motion filter and to the BA's second flow term.  An addition: the reference's only
+ * real tracker wraps a closed CUDA package.  tests/klt_reference.py restates this arithmetic in float64.
+ *
+ * Common rules.  Pixel centres are at integer coordinates, x = column, y = row.  Every read outside an image
+ * replicates the border (indices clamped to [0, w-1] / [0, h-1]).  All arithmetic is f32, every product and sum
+ * rounded on its own (no contraction).
+ *   bilinear sample S(img, x, y): x0 = floor(x), fx = x - x0 (same for y); v00 = img[y0][x0], v01 = img[y0][x0+1],
+ *   v10 = img[y0+1][x0], v11 = img[y0+1][x0+1] (clamped indices); top = v00 + fx*(v01 - v00),
+ *   bot = v10 + fx*(v11 - v10); S = top + fy*(bot - top).
+ *   lambda_min(a, b, c) = 0.5*(a + c) - sqrt((0.5*(a - c))^2 + b^2), the smaller eigenvalue of [a b; b c].
+ * A pyramid of an H x W frame with L levels is ONE f32 buffer: level 0 [H,W] first, level l+1 of size
+ * ((h_l + 1)/2, (w_l + 1)/2) directly behind level l (`klt_ext.pyramid_layout` gives sizes and offsets).
+ * ------------------------------------------------------------------------------------------- */
+#define VIPE_KLT_OOB 1          /* a window centre of some level, or the final position, closer than `border` to an edge */
+#define VIPE_KLT_LOW_TEXTURE 2  /* lambda_min(G) / (2r+1)^2 at level 0 < min_eig */
+#define VIPE_KLT_RESIDUAL 4     /* level-0 mean |e| > max_residual */
+#define VIPE_KLT_FB 8           /* forward-backward distance > fb_thresh (or not finite) */
+#define VIPE_KLT_MASKED 16      /* mask at the rounded new position is 0 */
+#define VIPE_KLT_DIVERGED 32    /* displacement not finite, or |d| > max_flow */
+
+/* d_rgb [H,W,3], rgb_dtype VIPE_U8 or VIPE_F32 (values 0-1) -> d_pyr, L levels (1 <= L <= 6).
+ *   level 0: gray = (0.299*R + 0.587*G) + 0.114*B with R, G, B on the 0-255 scale (u8 as they are; f32: the sum of the
+ *            0-1 values, then * 255).
+ *   level l+1 (y, x): the separable binomial [1 4 6 4 1]/16 of level l at (2y, 2x).  Rows first: for each of the rows
+ *            2y-2 .. 2y+2 (clamped) t = (((p[-2] + p[2]) + 4*(p[-1] + p[1])) + 6*p[0]) * 0.0625 over the columns
+ *            2x-2 .. 2x+2 (clamped); then the same expression over the five t.
+ * d_rgb and d_pyr must be 16-byte aligned.  One launch per level: level 0 reads the frame once (four pixels per thread,
+ * 16-byte stores), every further level reads a quarter of the one before. */
+int vipe_klt_pyramid(const void* d_rgb, int rgb_dtype, int H, int W, int L, float* d_pyr, void* stream);
+
+/* Corner detection on level 0 (d_img [H,W] f32, the head of a pyramid).  gx = 0.5*(I[y][x+1] - I[y][x-1]),
+ * gy = 0.5*(I[y+1][x] - I[y-1][x]) (clamped indices); (a, b, c) = sums of (gx*gx, gx*gy, gy*gy) over the 5 x 5
+ * neighbourhood, pixels outside the image contributing zero, summed row by row, left to right;
+ * response = lambda_min(a, b, c).  The image is cut into cell x cell cells (4 <= cell <= 32; ncx = ceil(W / cell)
+ * columns, ncy = ceil(H / cell) rows of cells, the last ones ragged).  Per cell, d_out [ncy*ncx,3] gets (x, y, response)
+ * of the pixel of largest response among those with border <= x <= W-1-border, border <= y <= H-1-border,
+ * d_mask[y][x] != 0 (d_mask [H,W] bytes or NULL) and response / 25 >= min_eig; ties go to the lowest row, then the
+ * lowest column.  A cell without such a pixel, and every cell with d_cell_busy[cell] != 0 (d_cell_busy [ncy*ncx] bytes
+ * or NULL), gets (-1, -1, 0).  One workgroup per cell: the products of the cell and its 2-pixel apron in LDS, an
+ * order-fixed argmax (no float atomics; the result does not depend on launch order). */
+int vipe_klt_detect(const float* d_img, int H, int W, const unsigned char* d_mask, const unsigned char* d_cell_busy,
+                    int cell, int border, float min_eig, float* d_out, void* stream);
+
+/* Tracks N points from pyramid A to pyramid B (both of H x W frames, L levels), coarse to fine, in one launch.
+ * For p = d_pts[n], d = 0, and l = L-1 .. 0:
+ *   c = p * 2^-l; for every window offset o in [-r, r]^2 (r = win_radius, 2 <= r <= 7):
+ *     I(o) = S(A_l, c + o), gx(o) = 0.5*(S(A_l, c + o + (1,0)) - S(A_l, c + o - (1,0))), gy likewise with (0,1);
+ *   G = (a, b, c) = sums of (gx*gx, gx*gy, gy*gy), det = a*c - b*b;
+ *   n_iters times: e(o) = I(o) - S(B_l, (c + d) + o); (bx, by) = sums of (e*gx, e*gy);
+ *     u = ((c*bx - b*by) / det, (a*by - b*bx) / det), or 0 unless det > 0; d += u;
+ *     with eps > 0 the iterations of this level stop after the update with |u|^2 < eps^2 (eps = 0: exactly n_iters);
+ *   OOB if c or q = c + d is not inside [border * 2^-l, (w_l - 1) - border * 2^-l] x [.., (h_l - 1) - ..];
+ *   d *= 2 unless l == 0.
+ * Then q = p + d -> d_out[n]; residual = sum |I(o) - S(B_0, q + o)| / (2r+1)^2 -> d_resid[n]; status bits OOB,
+ * LOW_TEXTURE (G of level 0), RESIDUAL, DIVERGED (d not finite or |d|^2 > max_flow^2) and, with d_mask (the mask of
+ * frame B, [H,W] bytes or NULL) and q rounded (floor(q + 0.5)) inside the image, MASKED.
+ *   d_fb_ref == NULL (forward pass): d_status[n] = those bits.  d_cell_busy is not touched.
+ *   d_fb_ref != NULL (backward pass: A and B swapped, d_pts the forward results, d_fb_ref [N,2] the original points,
+ *     d_mask ignored): d_status[n] is READ, the bits of this pass are not added, VIPE_KLT_FB is added unless
+ *     |q - d_fb_ref[n]|^2 <= fb_thresh^2, and the byte is written back.  If it is 0 and d_cell_busy != NULL
+ *     ([ncy*ncx] bytes, cells of `cell` pixels as in vipe_klt_detect, 4 <= cell), the cell that holds d_pts[n] rounded
+ *     is set to 1 (plain byte stores; racing writers store the same value).
+ * d_out [N,2] f32, d_status [N] bytes, d_resid [N] f32.  N == 0: VIPE_OK, no launch.  Null pointers, r outside 2..7,
+ * L outside 1..6, n_iters outside 1..100: VIPE_EINVAL.  One wave per point, four points per workgroup: the (2r+1)^2
+ * window pixels are spread over the 64 lanes (up to four per lane), template and gradients stay in registers, the sums
+ * go through cross-lane butterflies (every lane holds the same total); no LDS. */
+int vipe_klt_track(const float* d_pyr_a, const float* d_pyr_b, int H, int W, int L, const float* d_pts, int N,
+                   const float* d_fb_ref, const unsigned char* d_mask, int win_radius, int n_iters, float eps, int border,
+                   float min_eig, float max_residual, float fb_thresh, float max_flow, int cell, float* d_out,
+                   unsigned char* d_status, float* d_resid, unsigned char* d_cell_busy, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -54,6 +54,9 @@ class SLAMConfig:
     disp_uncertainty: bool = False  # marginal covariances of the last global BA (`SLAMOutput.keyframe_disp_var` /
                                     # `keyframe_pose_cov`): one `FactorGraph.marginals` call per clip after the last backend
                                     # pass, with that pass's BA arguments.  Off: nothing is allocated, no launch differs
+    sparse_tracks: str = None      # "klt": `run` builds a `KLTSparseTracks(n_views)` (corners + pyramidal Lucas-Kanade in
+                                   # HIP) when the caller passed no tracker - the motion filter's track score and the BA's
+                                   # track term get real tracks.  None: no tracker is built, nothing is launched or changed
     backend_lock_path: str = None        # ... and let their global-BA phases - each fills the chip by itself and wants the
                                          # pyramid budget to itself - take turns (an advisory file lock held around the two
                                          # backend passes), while the other clips' pass 1 / pass 2 run beside it
@@ -79,6 +82,8 @@ class SLAMSystem:
         self.droid_net = droid_net if droid_net is not None else DroidNet()
         self.metric_depth = depth_model  # system.py:114-127 builds it from `keyframe_depth`; here the caller's
         self.sparse_tracks = sparse_tracks
+        assert self.config.sparse_tracks in (None, "klt"), "SLAMConfig.sparse_tracks: None or 'klt'"
+        self._config_tracker = sparse_tracks is None and self.config.sparse_tracks == "klt"  # then a fresh one per run
         self._resizes = None  # one `StandardResize` per view inside `run(..., native_resolution=True)`, None outside it
         # system.py:91 builds a tracker from the config; here the caller's (`track_image(frames)` per frame of pass 1,
         # `enabled`, `compute_dense_disp_target_weight` for the BA's track term) or None = the reference's dummy
@@ -268,6 +273,8 @@ class SLAMSystem:
         `sparse_tracks` tracker is handed the frames as they came (`track_image`), while the reference's sees the
         resized, cropped ones: in native mode its `observations` must be in `StandardResize(...).out_size` pixel
         coordinates (resize its input, or map its tracks with `forward_intrinsics`' scale and crop) - not converted here.
+        A tracker with `accepts_resize` (`KLTSparseTracks`) is handed the per-view `StandardResize` (`set_resize`) and
+        does that mapping itself.
 
         With `SLAMConfig.upsample_disps` the output carries `keyframe_disps_up` [N_kf,V,H,W] and
         `keyframe_disps_up_valid` [N_kf,V] (aligned with `keyframe_ids`), at SLAM resolution: with native_resolution=True
@@ -291,6 +298,11 @@ class SLAMSystem:
                 assert tuple(f.rgb.shape[:2]) == (height, width), "all views must share one frame size"
             resizes = [StandardResize(height, width) for _ in range(n_views)]
             height, width = resizes[0].out_size
+        if self._config_tracker:
+            from .sparse_tracks import KLTSparseTracks
+            self.sparse_tracks = KLTSparseTracks(n_views, device=self.device)
+        if resizes is not None and getattr(self.sparse_tracks, "accepts_resize", False):
+            self.sparse_tracks.set_resize(resizes)  # it tracks at the native size and reports at `out_size`
         self.config.frontend.has_init_pose = frames[0][0].pose is not None
         self._build_components(height, width, n_views, rig, camera_type)
         b = self.buffer
