@@ -52,6 +52,12 @@ extern "C" {
 
 #define VIPE_CAM_PINHOLE 0 /* vipe/utils/cameras.py:123 */
 #define VIPE_CAM_MEI 1     /* vipe/utils/cameras.py:220 */
+#define VIPE_CAM_PANORAMA 2 /* CameraType.PANORAMA, vipe/utils/cameras.py:357-396: 360-degree equirectangular grid, pixel-centre
+                               convention u_n = (u + 0.5) / wd; disparity is inverse RANGE; no intrinsics (the [V,4] row is all
+                               zero and never read, though the pointer is checked like any other; optimize_intrinsics with it is VIPE_EINVAL).  The reference defines the rays
+                               (iproj_disp, :366-387) and the projection (vipe/utils/geometry.py:89-120) but no proj_points; the
+                               Jacobian, the validity rule (range > 0.1, 1e-3 off the poles) and the wrapping of horizontal
+                               differences at the seam are stated in csrc/camera.cuh. */
 
 /* library / build identification ("gfx950", ABI version) */
 const char* vipe_amd_version(void);
@@ -353,6 +359,20 @@ int vipe_frame_distance_rig(const float* d_poses, const float* d_rig, const floa
  * poses [n,7], disps [n,ht,wd], intrinsics [4], inds [num] int64, thresh [num] f32, counter [num,ht,wd] f32. */
 int vipe_depth_filter(const float* d_poses, const float* d_disps, const float* d_intrinsics, const int64_t* d_inds,
                       const float* d_thresh, float* d_counter, int n, int num, int ht, int wd, void* stream);
+
+/* The same three operations for VIPE_CAM_PANORAMA (csrc/sphere_ops.hip); there are no intrinsics to pass.
+ * vipe_frame_distance_sphere: vipe_frame_distance_rig (buffer.py:550-593, geom_kernels.cu:560-676) on the sphere - flow in
+ * pixels of the grid with the horizontal part wrapped at the seam, validity by range and pole distance.
+ * vipe_depth_filter_sphere: vipe_depth_filter (geom_kernels.cu:678-793) - the inverse range in the neighbour frame against
+ * its four bilinear neighbours, columns wrapped, rows not.
+ * vipe_iproj_sphere: vipe_iproj (geom_kernels.cu:795-861) - points act(pose, (ray, d)) / d with the ray of
+ * cameras.py:378-386. */
+int vipe_frame_distance_sphere(const float* d_poses, const float* d_rig, const float* d_disps, const int64_t* d_pi,
+                               const int64_t* d_qi, const int64_t* d_pj, const int64_t* d_qj, float* d_dist, int M,
+                               int n_views, int ht, int wd, float beta, int bidirectional, void* stream);
+int vipe_depth_filter_sphere(const float* d_poses, const float* d_disps, const int64_t* d_inds, const float* d_thresh,
+                             float* d_counter, int n, int num, int ht, int wd, void* stream);
+int vipe_iproj_sphere(const float* d_poses, const float* d_disps, float* d_points, int n, int ht, int wd, void* stream);
 
 /* projmap: replaces projmap_cuda, geom_kernels.cu:1436-1460 (kernel :434-519). coords [E,ht,wd,3], valid [E,ht,wd,1]. */
 int vipe_projmap(const float* d_poses, const float* d_disps, const float* d_intrinsics, const int64_t* d_ii,

@@ -17,7 +17,7 @@ LIB_PATH = os.path.join(HERE, "lib", "libvipe_amd.so")
 
 F16, F32, F64 = 0, 1, 2
 DTYPE_CODE = {torch.float16: F16, torch.float32: F32, torch.float64: F64}
-CAMERA_CODE = {"pinhole": 0, "mei": 1}
+CAMERA_CODE = {"pinhole": 0, "mei": 1, "panorama": 2}  # VIPE_CAM_*; the names are the reference's CameraType values
 
 
 def parse_struct(name, path=HEADER):

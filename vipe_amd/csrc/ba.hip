@@ -84,13 +84,15 @@ int overlap_piece(const vipe_ba_params& p, hipEvent_t ev, int piece, int n_piece
 }
 
 // The <CAM, F> instantiation of a call: camera model and F = shared intrinsics unknowns of a mono system (1 + D when
-// optimize_intrinsics, else 0).  fn(CamF<CAM, F>{}) is called with the one that applies.
+// optimize_intrinsics, else 0; the panorama has no intrinsics - check_live_call).  fn(CamF<CAM, F>{}) is called with the
+// one that applies.
 template <int CAM_, int F_>
 struct CamF { static constexpr int CAM = CAM_, F = F_; };
 template <class Fn>
 auto with_cam_f(const BAArgs& a, Fn&& fn) {
   const bool intr = a.p.optimize_intrinsics != 0;
   if (a.p.camera == VIPE_CAM_PINHOLE) return intr ? fn(CamF<VIPE_CAM_PINHOLE, 1>{}) : fn(CamF<VIPE_CAM_PINHOLE, 0>{});
+  if (a.p.camera == VIPE_CAM_PANORAMA) return fn(CamF<VIPE_CAM_PANORAMA, 0>{});
   return intr ? fn(CamF<VIPE_CAM_MEI, 2>{}) : fn(CamF<VIPE_CAM_MEI, 0>{});
 }
 
@@ -211,10 +213,11 @@ void bind_arrays(BAArgs& a, float* poses, float* disps, float* intr, float* rig,
 // The parameters of a live call.  a: what bind_arrays bound, for a call that reads the state and the terms (null:
 // vipe_dense_ba_marginals); iterates: n_iters counts (vipe_dense_ba)
 int check_live_call(const vipe_ba_params& p, const BAArgs* a, bool iterates) {
+  VIPE_CHECK_ARG(p.camera == VIPE_CAM_PINHOLE || p.camera == VIPE_CAM_MEI || p.camera == VIPE_CAM_PANORAMA);
+  VIPE_CHECK_ARG(!(p.camera == VIPE_CAM_PANORAMA && p.optimize_intrinsics));  // the panorama has none; its row is never read
   VIPE_CHECK_ARG(!a || (a->poses && a->disps && a->sens && a->intr && a->rig && a->eta));
   VIPE_CHECK_ARG(p.n_poses > 0 && p.n_views > 0 && p.ht > 0 && p.wd > 0 && p.M >= 0 && !(iterates && p.n_iters < 0));
   VIPE_CHECK_ARG(!a || (p.t0 <= p.t1 && p.intr_factor > 0));
-  VIPE_CHECK_ARG(p.camera == VIPE_CAM_PINHOLE || p.camera == VIPE_CAM_MEI);
   VIPE_CHECK_ARG(!a || p.M == 0 || (a->target && a->weight && a->pi && a->qi && a->pj && a->qj && a->di));
   if (is_multiview(p) && p.n_views > RG_VMAX) return VIPE_EUNSUPPORTED;  // rigs of up to 8 cameras
   if ((int64_t)p.n_poses * p.n_views > 65535) return VIPE_EINVAL;

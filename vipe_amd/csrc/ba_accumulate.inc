@@ -41,9 +41,10 @@ typedef float float4m __attribute__((ext_vector_type(4)));
 // map Lm / gcol, its own R1 rows and its tail rows.
 
 // term_setup plus the map of the mono kernels: column c of Mi = [pi == pj: e_c] - Adj(G_ij)^T e_c
+template <int CAM>
 __device__ __forceinline__ void term_setup_m(const BAArgs& a, int e, TermGeomM& m) {
   TermGeom& g = m.g;
-  term_setup(a, e, g);
+  term_setup<CAM>(a, e, g);
 #pragma unroll
   for (int c = 0; c < 6; ++c) {
     float ec[6] = {0, 0, 0, 0, 0, 0}, col[6];
@@ -61,7 +62,7 @@ struct WalkPixel {
   static constexpr int FF = F > 0 ? F : 1;
   int p;     // clamped to P - 1 ...
   bool inb;  // ... for the lanes past the image, whose weights are 0 and which store nothing
-  float d, X0, Y0, dX0[FF], dY0[FF];
+  float d, X0, Y0, Z0, dX0[FF], dY0[FF];  // Z0: the panorama's; pinhole / MEI rays have the constant 1 (transform_ray)
   float C, wz, Ei[6], Efr[FF];  // C_k, w_k, E_kk, E_f (rigs: the intrinsics of the source view)
 };
 
@@ -71,10 +72,11 @@ __device__ __forceinline__ WalkPixel<F> walk_pixel(const BAArgs& a, int k, int q
   const int p_raw = blockIdx.x * TILE + threadIdx.x;
   px.inb = p_raw < a.P;
   px.p = px.inb ? p_raw : a.P - 1;
-  const cam::Intr Ii = cam::load_scaled(a.intr + qi * (4 + a.D), a.D, 1.0f / a.p.intr_factor);
+  const cam::Intr Ii = cam::load<CAM>(a.intr + qi * (4 + a.D), a.D, 1.0f / a.p.intr_factor, a.p.ht, a.p.wd);
   const float u = (float)(px.p % a.p.wd), v = (float)(px.p / a.p.wd);
   px.d = a.disps[(int64_t)k * a.P + px.p];
-  cam::iproj<CAM, F>(Ii, u, v, px.X0, px.Y0, px.dX0, px.dY0);
+  px.Z0 = 1.0f;
+  cam::iproj<CAM, F>(Ii, u, v, px.X0, px.Y0, px.Z0, px.dX0, px.dY0);
   px.C = px.wz = 0.f;
 #pragma unroll
   for (int q = 0; q < 6; ++q) px.Ei[q] = 0.f;
@@ -83,15 +85,15 @@ __device__ __forceinline__ WalkPixel<F> walk_pixel(const BAArgs& a, int k, int q
   return px;
 }
 
-// Pixel px seen through term G: depth Z in the target view, projection (x, y) with its Jacobians by the point (Jp) and
+// Pixel px seen through term G: the point X1 in the target view, projection (x, y) with its Jacobians by the point (Jp) and
 // by the target view's intrinsics (Jfj), and Ja = d point / d pose_j (with the rig adjoint where R_qj is not the identity)
 template <int CAM, int F>
-__device__ __forceinline__ void term_point_jacobians(const TermGeom& G, const WalkPixel<F>& px, float& Z, float& x, float& y,
-                                                     float (&Jp)[2][3], float (&Jfj)[2][WalkPixel<F>::FF], float (&Ja)[3][6]) {
-  const float X0 = px.X0, Y0 = px.Y0, d = px.d;
-  const float X = G.T.R[0] * X0 + G.T.R[1] * Y0 + G.T.R[2] + G.T.t[0] * d;
-  const float Y = G.T.R[3] * X0 + G.T.R[4] * Y0 + G.T.R[5] + G.T.t[1] * d;
-  Z = G.T.R[6] * X0 + G.T.R[7] * Y0 + G.T.R[8] + G.T.t[2] * d;
+__device__ __forceinline__ void term_point_jacobians(const TermGeom& G, const WalkPixel<F>& px, float (&X1)[3], float& x,
+                                                     float& y, float (&Jp)[2][3], float (&Jfj)[2][WalkPixel<F>::FF],
+                                                     float (&Ja)[3][6]) {
+  const float d = px.d;
+  transform_ray<CAM>(G.T, px.X0, px.Y0, px.Z0, d, X1[0], X1[1], X1[2]);
+  const float X = X1[0], Y = X1[1], Z = X1[2];
   cam::proj<CAM, true, F>(G.Ij, X, Y, Z, x, y, Jp, Jfj);
   const float J0[3][6] = {{d, 0, 0, 0, Z, -Y}, {0, d, 0, -Z, 0, X}, {0, 0, d, Y, -X, 0}};
 #pragma unroll
@@ -174,13 +176,13 @@ __device__ __forceinline__ void walk_tile(const BAArgs& a, const TermGeomM* tg, 
       if (t >= deg) break;  // workgroup-uniform
       const TermGeom& G = tg[t].g;
       const int e = G.e;
-      float Z, x, y, Jp[2][3], Jfj[2][FF], Ja[3][6];
-      term_point_jacobians<CAM, F>(G, px, Z, x, y, Jp, Jfj, Ja);
+      float X1[3], x, y, Jp[2][3], Jfj[2][FF], Ja[3][6];
+      term_point_jacobians<CAM, F>(G, px, X1, x, y, Jp, Jfj, Ja);
       const float2 tgt = cur_t[uu], wg = cur_w[uu];
-      const float val = valid_weight(a, Z, inb);  // geom.py:263, buffer.py:413
+      const float val = valid_weight<CAM>(a, X1, inb);  // geom.py:263, buffer.py:413
       const float wd2[2] = {val * wg.x, val * wg.y};                     // weights of the disparity system
       const float wc[2] = {G.merge == 2 ? 0.0f : wd2[0], G.merge == 2 ? 0.0f : wd2[1]};  // ... of the pose blocks
-      const float rc[2] = {x - tgt.x, y - tgt.y};
+      const float rc[2] = {cam::wrap_dx<CAM>(x - tgt.x, G.Ij.cx), y - tgt.y};
       const bool fj = G.sj >= 0;
       float Ejv[6] = {0, 0, 0, 0, 0, 0};
 #pragma unroll
@@ -386,7 +388,7 @@ __global__ __launch_bounds__(TILE) __attribute__((amdgpu_waves_per_eu(3, 3))) vo
   for (int i = tid; i < AM_ROWS * AM_SP + AM_DMAX * 256 + 64; i += TILE) accS[i] = 0.0f;
   if (tid < deg) {
     TermGeomM m;
-    term_setup_m(a, w.order[beg + tid], m);
+    term_setup_m<CAM>(a, w.order[beg + tid], m);
     tg[tid] = m;
   }
   __syncthreads();
@@ -552,7 +554,7 @@ __global__ __launch_bounds__(TILE) void ba_walk_kernel(BAArgs a) {
     for (int i = tid; i < WK_CH1 * 256; i += TILE) acc1[i] = 0.0f;
     if (tid < deg) {
       TermGeomM m;
-      term_setup_m(a, w.order[beg + cb + tid], m);
+      term_setup_m<CAM>(a, w.order[beg + cb + tid], m);
       tg[tid] = m;
     }
     __syncthreads();
@@ -640,7 +642,7 @@ __global__ __launch_bounds__(TILE) void ba_walk_rig_kernel(BAArgs a) {
       const int e = w.order[beg + cb + tid];
       const int pi = (int)a.pi[e], pj = (int)a.pj[e], qj = (int)a.qj[e];
       term_transforms(a.poses, a.rig, pi, qi, pj, qj, m.g.T, m.g.G, m.g.Rr);
-      m.g.Ij = cam::load_scaled(a.intr + qj * (4 + a.D), a.D, 1.0f / prm.intr_factor);
+      m.g.Ij = cam::load<CAM>(a.intr + qj * (4 + a.D), a.D, 1.0f / prm.intr_factor, prm.ht, prm.wd);
       m.g.e = e;
       m.g.merge = (pi == pj);
       m.g.rig_adj = !(m.g.Rr.t[0] == 0.f && m.g.Rr.t[1] == 0.f && m.g.Rr.t[2] == 0.f && m.g.Rr.R[0] == 1.f &&
@@ -683,13 +685,13 @@ __global__ __launch_bounds__(TILE) void ba_walk_rig_kernel(BAArgs a) {
       const TermGeom& G = tg[t].g;
       const int e = G.e, qj = tg[t].qj;
       const bool same = tg[t].same_view;
-      float Z, x, y, Jp[2][3], Jfj[2][F], Ja[3][6];
-      term_point_jacobians<CAM, F>(G, px, Z, x, y, Jp, Jfj, Ja);
+      float X1[3], x, y, Jp[2][3], Jfj[2][F], Ja[3][6];
+      term_point_jacobians<CAM, F>(G, px, X1, x, y, Jp, Jfj, Ja);
       float2 tgt, wg;
       load_tw(a, e, p, P, tgt, wg);
-      const float val = valid_weight(a, Z, inb);  // geom.py:263, buffer.py:413
+      const float val = valid_weight<CAM>(a, X1, inb);  // geom.py:263, buffer.py:413
       const float wc[2] = {val * wg.x, val * wg.y};
-      const float rc[2] = {x - tgt.x, y - tgt.y};
+      const float rc[2] = {cam::wrap_dx<CAM>(x - tgt.x, G.Ij.cx), y - tgt.y};
       float Ejv[6] = {0, 0, 0, 0, 0, 0};
 #pragma unroll
       for (int c = 0; c < 2; ++c) {

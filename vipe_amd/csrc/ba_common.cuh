@@ -123,16 +123,19 @@ __device__ __forceinline__ void load_tw(const BAArgs& a, int e, int p, int P, fl
     wg = *reinterpret_cast<const float2*>(a.weight + o2);
   }
 }
-// validity weight: live z0... target-side z > 0.1 (geom.py:263); DROID !(z < 0.25) (geom_kernels.cu:33,304)
-__device__ __forceinline__ float valid_weight(const BAArgs& a, float Z, bool inb) {
-  const bool ok = a.droid ? !(Z < 0.25f) : (Z > cam::MIN_DEPTH);
+// validity weight: live z0... target-side z > 0.1 (geom.py:263; the panorama's range and pole test, camera.cuh); DROID
+// !(z < 0.25) (geom_kernels.cu:33,304)
+template <int CAM>
+__device__ __forceinline__ float valid_weight(const BAArgs& a, const float (&X1)[3], bool inb) {
+  const bool ok = a.droid ? !(X1[2] < 0.25f) : cam::valid_point<CAM>(X1[0], X1[1], X1[2]);
   return (inb && ok) ? a.p.weight_scale : 0.0f;
 }
 // per-term transforms incl. the DROID stereo term (ii == jj: fixed baseline, no pose blocks; geom_kernels.cu:222-233)
+template <int CAM>
 __device__ __forceinline__ void term_setup(const BAArgs& a, int e, TermGeom& g) {
   const int pi = (int)a.pi[e], pj = (int)a.pj[e], qj = (int)a.qj[e];
   term_transforms(a.poses, a.rig, pi, (int)a.qi[e], pj, qj, g.T, g.G, g.Rr);
-  g.Ij = cam::load_scaled(a.intr + qj * (4 + a.D), a.D, 1.0f / a.p.intr_factor);
+  g.Ij = cam::load<CAM>(a.intr + qj * (4 + a.D), a.D, 1.0f / a.p.intr_factor, a.p.ht, a.p.wd);
   g.e = e;
   g.merge = (pi == pj);
   if (a.droid && pi == pj) {

@@ -29,8 +29,8 @@ __global__ __launch_bounds__(256) void reproject_kernel(ReprojArgs a) {
     const int pi = (int)a.pi[e], qi = (int)a.qi[e], pj = (int)a.pj[e], qj = (int)a.qj[e];
     Rigid G, Rr;
     term_transforms(a.poses, a.rig, pi, qi, pj, qj, T, G, Rr);
-    Ii = cam::load_scaled(a.intr + qi * (4 + a.D), a.D, a.inv_factor);
-    Ij = cam::load_scaled(a.intr + qj * (4 + a.D), a.D, a.inv_factor);
+    Ii = cam::load<CAM>(a.intr + qi * (4 + a.D), a.D, a.inv_factor, a.ht, a.wd);
+    Ij = cam::load<CAM>(a.intr + qj * (4 + a.D), a.D, a.inv_factor, a.ht, a.wd);
     dframe = (int)a.di[e];
   }
   __syncthreads();
@@ -38,19 +38,22 @@ __global__ __launch_bounds__(256) void reproject_kernel(ReprojArgs a) {
   if (p >= P) return;
   const float u = (float)(p % a.wd), v = (float)(p / a.wd);
   const float d = a.disps[(int64_t)dframe * P + p];
-  float X0, Y0, dX[1], dY[1];
-  cam::iproj<CAM, 0>(Ii, u, v, X0, Y0, dX, dY);
-  const float X = T.R[0] * X0 + T.R[1] * Y0 + T.R[2] + T.t[0] * d;
-  const float Y = T.R[3] * X0 + T.R[4] * Y0 + T.R[5] + T.t[1] * d;
-  const float Z = T.R[6] * X0 + T.R[7] * Y0 + T.R[8] + T.t[2] * d;
+  float X0, Y0, Z0 = 1.0f, dX[1], dY[1];
+  cam::iproj<CAM, 0>(Ii, u, v, X0, Y0, Z0, dX, dY);
+  float X, Y, Z;
+  transform_ray<CAM>(T, X0, Y0, Z0, d, X, Y, Z);
   float x, y, Jp[2][3], Jf[2][1];
   cam::proj<CAM, false, 0>(Ij, X, Y, Z, x, y, Jp, Jf);
+  const bool ok = cam::valid_point<CAM>(X, Y, Z);  // pinhole / MEI: X0.z == 1 > MIN_DEPTH (geom.py:263)
+  if constexpr (CAM == VIPE_CAM_PANORAMA) {
+    if (!ok) { x = u; y = v; }  // no clamp for this camera: an invalid pixel keeps its own place
+  }
   const int64_t o = (int64_t)e * P + p;
   reinterpret_cast<float2*>(a.coords)[o] = make_float2(x, y);
-  if (a.valid) a.valid[o] = (Z > cam::MIN_DEPTH) ? 1.0f : 0.0f;  // X0.z == 1 > MIN_DEPTH (geom.py:263)
+  if (a.valid) a.valid[o] = ok ? 1.0f : 0.0f;
   if constexpr (MOTN != 0) {
     const float2 tg = reinterpret_cast<const float2*>(a.target)[o];
-    float m[4] = {x - u, y - v, tg.x - x, tg.y - y};  // factor_graph.py:259
+    float m[4] = {cam::wrap_dx<CAM>(x - u, Ij.cx), y - v, cam::wrap_dx<CAM>(tg.x - x, Ij.cx), tg.y - y};  // factor_graph.py:259
     if constexpr (MOTN == 3) {
       typedef _Float16 half4v __attribute__((ext_vector_type(4)));
       half4v hv;
@@ -74,6 +77,7 @@ int launch(const ReprojArgs& a, int camera, hipStream_t s) {
   dim3 grid((a.ht * a.wd + 255) / 256, a.M), block(256);
   if (camera == VIPE_CAM_PINHOLE) reproject_kernel<VIPE_CAM_PINHOLE, MOTN><<<grid, block, 0, s>>>(a);
   else if (camera == VIPE_CAM_MEI) reproject_kernel<VIPE_CAM_MEI, MOTN><<<grid, block, 0, s>>>(a);
+  else if (camera == VIPE_CAM_PANORAMA) reproject_kernel<VIPE_CAM_PANORAMA, MOTN><<<grid, block, 0, s>>>(a);
   else return VIPE_EINVAL;
   return vipe_launch_status();
 }

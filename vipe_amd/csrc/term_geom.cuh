@@ -24,7 +24,7 @@ struct TermGeom {
   Rigid T;    // full transform acting on X0
   Rigid G;    // G_ij = G_pj * G_pi^-1          (for Ji = -Adj(G_ij)^T Jj, geom.py:277)
   Rigid Rr;   // R_qj^-1                        (Ja rows <- Adj(R_qj^-1)^T, geom.py:273)
-  cam::Intr Ij;  // target-view intrinsics at 1/8 scale
+  cam::Intr Ij;  // target-view intrinsics at 1/8 scale (panorama: the grid)
   int e;      // term index
   int sj;     // slot of pose pj in the reduced system, -1 if fixed
   int merge;  // pi == pj: Jj is added to Ji (same variable block)
@@ -41,6 +41,22 @@ __device__ __forceinline__ void term_transforms(const float* poses, const float*
   T = to_rigid(Tt);
   G = to_rigid(Gij);
   Rr = to_rigid(Rji);
+}
+
+// X1 = R (X0, Y0, Z0) + t d.  Pinhole / MEI rays have Z0 == 1: their third column is added as it stands, the operations
+// and their order those kernels have always had
+template <int CAM>
+__device__ __forceinline__ void transform_ray(const Rigid& T, float X0, float Y0, float Z0, float d, float& X, float& Y,
+                                              float& Z) {
+  if constexpr (CAM == VIPE_CAM_PANORAMA) {
+    X = T.R[0] * X0 + T.R[1] * Y0 + T.R[2] * Z0 + T.t[0] * d;
+    Y = T.R[3] * X0 + T.R[4] * Y0 + T.R[5] * Z0 + T.t[1] * d;
+    Z = T.R[6] * X0 + T.R[7] * Y0 + T.R[8] * Z0 + T.t[2] * d;
+  } else {
+    X = T.R[0] * X0 + T.R[1] * Y0 + T.R[2] + T.t[0] * d;
+    Y = T.R[3] * X0 + T.R[4] * Y0 + T.R[5] + T.t[1] * d;
+    Z = T.R[6] * X0 + T.R[7] * Y0 + T.R[8] + T.t[2] * d;
+  }
 }
 
 // b = Adj(X)^T a for X = (R,t):  [R^T a1, R^T (a2 - t x a1)]   (se3.h:83)

@@ -87,6 +87,14 @@ def update_finish(coords1, dw, mask, target, weight, eta, du, damping):
                                    E, n_src, ht, wd, stream_ptr(coords1)), "update_finish")
 
 
+def _check_camera_options(camera, optimize_intrinsics):
+    """The argument errors the library answers with VIPE_EINVAL, raised before anything touches the device."""
+    if camera not in CAMERA_CODE:
+        raise ValueError(f"unknown camera {camera!r} (one of {sorted(CAMERA_CODE)})")
+    if camera == "panorama" and optimize_intrinsics:
+        raise ValueError("the panorama camera has no intrinsics: optimize_intrinsics cannot be combined with it")
+
+
 BA_OPT_ONE_CHAIN, BA_OPT_GENERAL_ACCUMULATE = 1, 2  # VIPE_BA_OPT_* (include/vipe_amd.h)
 PROFILE_EVENTS = None  # measurement aid (bench.py): (event, event[, iteration]) every dense_ba call records around that iteration's accumulate launch
 PLAN_REUSE = True  # False: rebuild the edge plan on every call and launch every kernel of both paths (validation aid)
@@ -107,6 +115,7 @@ def dense_ba(poses, disps, disps_sens, intrinsics, rig, target, weight, disp_dam
     poses [>=n_poses,7]; disps, disps_sens, disp_damping [>=n_poses*V,ht,wd] (flattened views);
     target, weight [M,ht*wd,2]; pi..di [M] int64.  `n_poses` bounds the pose/frame indices that occur
     (default: all rows of `poses`); a tight bound keeps the reduced system small."""
+    _check_camera_options(camera, optimize_intrinsics)
     check_gpu_contig(poses, disps, disps_sens, intrinsics, rig, target, weight, disp_damping, pi, qi, pj, qj, di)
     for t in (poses, disps, disps_sens, intrinsics, rig, target, weight, disp_damping):
         require(t.dtype == torch.float32, "dense_ba works in float32 (the reference's BA dtype)")
@@ -177,6 +186,7 @@ def dense_ba_linearize(poses, disps, disps_sens, intrinsics, rig, target, weight
     at the given state, which is only read.  -> (S, info, ctx): the damped symmetric reduced system [n,n] float64
     (n = info[3]; reading it back synchronises the stream once), the plan's facts, and what `dense_ba_marginals_apply`
     needs.  Nothing else may run in the workspace between the two halves."""
+    _check_camera_options(camera, optimize_intrinsics)
     check_gpu_contig(poses, disps, disps_sens, intrinsics, rig, target, weight, disp_damping, pi, qi, pj, qj, di)
     for t in (poses, disps, disps_sens, intrinsics, rig, target, weight, disp_damping):
         require(t.dtype == torch.float32, "dense_ba_marginals works in float32 (the reference's BA dtype)")
@@ -289,12 +299,23 @@ def frame_distance(poses, disps, intrinsics, pi, pj, qi, qj, di, beta):
     return dist
 
 
-def frame_distance_rig(poses, rig, disps, intrinsics, pi, qi, pj, qj, beta, bidirectional=True, intr_factor=8.0):
+def frame_distance_rig(poses, rig, disps, intrinsics, pi, qi, pj, qj, beta, bidirectional=True, intr_factor=8.0,
+                       camera="pinhole"):
     """[fused] buffer.py:550-593 in one launch: poses [N,7], rig [V,7], disps [N*V,ht,wd], intrinsics [V,4|5] at full
-    resolution, (pi, qi) -> (pj, qj) [M] int64 -> dist [M] (`vipe_frame_distance_rig`)."""
-    check_gpu_contig(poses, rig, disps, intrinsics, pi, qi, pj, qj)
+    resolution, (pi, qi) -> (pj, qj) [M] int64 -> dist [M] (`vipe_frame_distance_rig`).  camera="panorama": the same on the
+    sphere (`vipe_frame_distance_sphere`: flow in pixels of the grid, wrapped at the seam); `intrinsics` is not read."""
+    if camera not in CAMERA_CODE:
+        raise ValueError(f"unknown camera {camera!r} (one of {sorted(CAMERA_CODE)})")
     M = pi.shape[0]
     _, ht, wd = disps.shape
+    if camera == "panorama":
+        check_gpu_contig(poses, rig, disps, pi, qi, pj, qj)
+        dist = torch.empty(M, dtype=torch.float32, device=poses.device)
+        check(lib().vipe_frame_distance_sphere(ptr(poses), ptr(rig), ptr(disps), ptr(_i64(pi)), ptr(_i64(qi)), ptr(_i64(pj)),
+                                               ptr(_i64(qj)), ptr(dist), M, int(rig.shape[0]), ht, wd, float(beta),
+                                               int(bool(bidirectional)), stream_ptr(poses)), "frame_distance_sphere")
+        return dist
+    check_gpu_contig(poses, rig, disps, intrinsics, pi, qi, pj, qj)
     dist = torch.empty(M, dtype=torch.float32, device=poses.device)
     check(lib().vipe_frame_distance_rig(ptr(poses), ptr(rig), ptr(disps), ptr(intrinsics), int(intrinsics.shape[1]),
                                         float(intr_factor), ptr(_i64(pi)), ptr(_i64(qi)), ptr(_i64(pj)), ptr(_i64(qj)), ptr(dist),
@@ -312,6 +333,27 @@ def depth_filter(poses, disps, intrinsics, ix, thresh):
     check(lib().vipe_depth_filter(ptr(poses), ptr(disps), ptr(intrinsics), ptr(_i64(ix)), ptr(thresh), ptr(counter), n,
                                   num, ht, wd, stream_ptr(poses)), "depth_filter")
     return counter
+
+
+def depth_filter_sphere(poses, disps, ix, thresh):
+    """`depth_filter` for the panorama camera (`vipe_depth_filter_sphere`): disps are inverse ranges, the neighbour's four
+    bilinear neighbours wrap at the seam -> counter [num,ht,wd] float32."""
+    check_gpu_contig(poses, disps, ix, thresh)
+    n, ht, wd = disps.shape
+    num = ix.shape[0]
+    counter = torch.zeros((num, ht, wd), dtype=torch.float32, device=poses.device)
+    check(lib().vipe_depth_filter_sphere(ptr(poses), ptr(disps), ptr(_i64(ix)), ptr(thresh), ptr(counter), n, num, ht, wd,
+                                         stream_ptr(poses)), "depth_filter_sphere")
+    return counter
+
+
+def iproj_sphere(poses, disps):
+    """`iproj` for the panorama camera (`vipe_iproj_sphere`): act(pose, (ray, d)) / d -> points [n,ht,wd,3]."""
+    check_gpu_contig(poses, disps)
+    n, ht, wd = disps.shape
+    pts = torch.zeros((n, ht, wd, 3), dtype=torch.float32, device=poses.device)
+    check(lib().vipe_iproj_sphere(ptr(poses), ptr(disps), ptr(pts), n, ht, wd, stream_ptr(poses)), "iproj_sphere")
+    return pts
 
 
 def projmap(poses, disps, intrinsics, ii, jj):

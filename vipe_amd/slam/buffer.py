@@ -204,6 +204,8 @@ class GraphBuffer:
         if st is not None and getattr(st, "enabled", False):
             # buffer.py:422-447: a second flow term on the same edges, targets / weights from the caller's tracker
             assert V == 1, "This does not support cross-view tracking yet."
+            if self.camera_type == "panorama":
+                raise ValueError("the sparse-track term is pinhole only (its flow targets are not wrapped at the seam)")
             s_target, s_weight = st.compute_dense_disp_target_weight(
                 source_view_inds=qi, source_frame_inds=self.tstamp[pi + base], target_view_inds=qj,
                 target_frame_inds=self.tstamp[pj + base], image_size=(self.height, self.width),
@@ -223,6 +225,9 @@ class GraphBuffer:
 
     def _pinhole_intrinsics_8(self):
         """camera_model.pinhole() at 1/8 scale (cameras.py:209-213, 338-348; geom.py:335)."""
+        if self.camera_type == "panorama":
+            raise ValueError("the panorama camera has no pinhole calibration (K, K_dense_disp and the unfused frame "
+                             "distance are pinhole / MEI only)")
         intr = self.intrinsics[:, :4] / 8.0
         if self.camera_type == "mei":
             intr = intr.clone()
@@ -253,6 +258,8 @@ class GraphBuffer:
         from types import SimpleNamespace
         if depth_model is None:
             return
+        if self.camera_type == "panorama":
+            raise ValueError("depth models estimate pinhole depth from a focal length; the panorama camera has neither")
         if frame_idx is not None:
             frames = [int(frame_idx)]
         else:
@@ -305,8 +312,11 @@ class GraphBuffer:
         V = self.n_views
         if fused and self.poses.is_cuda:
             d = slam_ext.frame_distance_rig(self.poses, self.rig, self.flattened_disps, self.intrinsics, pi, qi, pj, qj, beta,
-                                            bidirectional)
+                                            bidirectional, camera=self.camera_type)
             return d.view(-1, V)
+        if self.camera_type == "panorama":
+            raise ValueError("the unfused frame distance is the reference's pinhole sequence; the panorama camera has the "
+                             "fused kernel only")
         poses = SE3(self.poses[: self.n_frames if n_frames is None else n_frames])
         rig = SE3(self.rig)
         # expand poses into (n v) space: R_v^-1 * G_n   (geom.py:338)
@@ -336,6 +346,18 @@ class GraphBuffer:
         for v in range(self.n_views):
             c2w_view = c2w * SE3(self.rig[v])[None]
             disps_v = self.disps[t_range, v].contiguous()
+            if self.camera_type == "panorama":  # rays of the sphere, inverse range; the seam wraps in the filter
+                ident = SE3.Identity(n, device=self.device).data.contiguous()
+                pts = slam_ext.iproj_sphere(ident if is_local else c2w_view.data.contiguous(), disps_v)
+                thresh_v = filter_thresh * (1.0 / disps_v.mean().item())
+                count = slam_ext.depth_filter_sphere(c2w_view.inv().data.contiguous(), disps_v,
+                                                     torch.arange(n, device=self.device),
+                                                     torch.full((n,), thresh_v, device=self.device))
+                masks = ((count >= min(2, n - 1)) & (disps_v > 0.5 * disps_v.mean(dim=[1, 2], keepdim=True))
+                         & (~self.masks[t_range, v]))
+                pts_list.append(pts)
+                mask_list.append(masks)
+                continue
             intr8 = self.intrinsics[v].clone()
             intr8[:4] = intr8[:4] / 8.0
             ident = SE3.Identity(n, device=self.device).data.contiguous()

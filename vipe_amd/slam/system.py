@@ -261,9 +261,38 @@ class SLAMSystem:
         mark("pass2_done_seconds")
         self.work["total"] = {k: _fg.WORK[k] - work0[k] for k in work0}
 
+    def _check_camera(self, camera_type, frames, native_resolution):
+        """What a camera model rules out, before anything is built or touches the device.  The panorama
+        (cameras.py:357-396) is the whole sphere on an equirectangular frame: no intrinsics (all-zero rows, as the
+        reference asserts), nothing that crops, and none of the parts that are pinhole by construction."""
+        from .._lib import CAMERA_CODE
+        if camera_type not in CAMERA_CODE:
+            raise ValueError(f"unknown camera_type {camera_type!r} (one of {sorted(CAMERA_CODE)})")
+        if camera_type != "panorama":
+            return
+        if native_resolution:
+            raise ValueError("camera_type='panorama': native_resolution crops the frame, which breaks the sphere - "
+                             "resize the equirectangular frames to multiples of 8 beforehand")
+        if self.sparse_tracks is not None or self._config_tracker:
+            raise ValueError("camera_type='panorama': the sparse-track term is pinhole only")
+        if self.config.backend.optimize_intrinsics:
+            raise ValueError("camera_type='panorama': the camera has no intrinsics to optimise")
+        if self.metric_depth is not None:
+            raise ValueError("camera_type='panorama': depth models estimate pinhole depth; the disparities of this "
+                             "camera are inverse ranges")
+        for f in frames[0]:
+            K = f.intrinsics
+            if K is None or tuple(K.shape) != (4,) or bool((K != 0).any()):
+                raise ValueError("camera_type='panorama': frames carry all-zero [4] intrinsics (cameras.py:360)")
+
     @torch.no_grad()
     def run(self, frames, rig=None, camera_type="pinhole", native_resolution=False):
         """frames: sequence (length T) of per-view lists of `Frame` (a single `Frame` per step for one view).
+
+        camera_type: "pinhole", "mei" or "panorama" (the reference's `CameraType` values).  A panorama clip is
+        equirectangular frames with all-zero `[4]` intrinsics; disparities are then inverse ranges (`Frame.metric_depth`,
+        if given, is the range), and `native_resolution`, a sparse tracker, `backend.optimize_intrinsics` and a depth
+        model are rejected (`ValueError`) before anything runs.  `SLAMMap.project_map` stays a pinhole target.
 
         native_resolution=False: the frames are at SLAM resolution already (sides multiples of 8) and the returned
         intrinsics are at that resolution.  True: frames of any size, as decoded - every view goes through the
@@ -292,6 +321,7 @@ class SLAMSystem:
             assert n_views == 1, "Need rig for multiple views"
             rig = SE3.Identity(1)
         height, width = frames[0][0].rgb.shape[:2]
+        self._check_camera(camera_type, frames, native_resolution)
         resizes = None
         if native_resolution:
             for f in frames[0]:  # system.py:222-223
