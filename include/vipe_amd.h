@@ -360,7 +360,7 @@ int vipe_frame_distance_rig(const float* d_poses, const float* d_rig, const floa
 int vipe_depth_filter(const float* d_poses, const float* d_disps, const float* d_intrinsics, const int64_t* d_inds,
                       const float* d_thresh, float* d_counter, int n, int num, int ht, int wd, void* stream);
 
-/* The same three operations for VIPE_CAM_PANORAMA (csrc/sphere_ops.hip); there are no intrinsics to pass.
+/* The same three operations for VIPE_CAM_PANORAMA (the Sphere family of csrc/geom_ops.hip); there are no intrinsics to pass.
  * vipe_frame_distance_sphere: vipe_frame_distance_rig (buffer.py:550-593, geom_kernels.cu:560-676) on the sphere - flow in
  * pixels of the grid with the horizontal part wrapped at the seam, validity by range and pole distance.
  * vipe_depth_filter_sphere: vipe_depth_filter (geom_kernels.cu:678-793) - the inverse range in the neighbour frame against

@@ -118,6 +118,25 @@ def test_projmap_and_iproj_beyond_one_workgroup(grid):
     assert tol > 0 and err <= tol
 
 
+def test_frame_ops_bits_unchanged():
+    """tests/golden/geom_parent_bits.npz holds what the eight frame geometry operations computed on the device before the
+    pinhole and the sphere kernels became two instantiations of one pixel walk (tests/golden/make_golden_geom_parent.py:
+    the inputs of this file and of tests/test_gpu_panorama.py, plus one per family at exactly 75 % valid pixels, where the
+    pinhole family answers 1000 and the sphere the mean).  No atomics, fixed-order reductions: the same bits, every array."""
+    import os
+    import sys
+    gold = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
+    sys.path.insert(0, gold)
+    import make_golden_geom_parent as mk
+    Z = np.load(os.path.join(gold, "geom_parent_bits.npz"))
+    got = mk.run_case()
+    assert sorted(got) == sorted(Z.files)
+    differ = [k for k in Z.files if not np.array_equal(got[k].view(np.uint32), Z[k].view(np.uint32))]
+    print("frame ops:", len(Z.files), "arrays,", "all equal" if not differ else f"DIFFERENT: {differ}")
+    assert not differ
+    assert Z["pinhole_quarter_invalid"][0] == 1000.0 and 0.0 < Z["panorama_quarter_invalid"][0] < 1000.0
+
+
 # ------------------------------------------------------------------------------------------------ scatter
 
 SLOTS = 37

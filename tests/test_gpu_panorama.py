@@ -249,7 +249,8 @@ def test_depth_filter_sphere():
     g, thresh = R.depth_filter_case()
     want, tie = R.depth_filter(g.poses_gt, g.disps_gt, np.arange(g.n), thresh)
     assert tie.mean() < SHARE_CAP
-    got = slam_ext.depth_filter_sphere(T(g.poses_gt), T(g.disps_gt), T(np.arange(g.n)), T(thresh.astype(np.float32)))
+    got = slam_ext.depth_filter(T(g.poses_gt), T(g.disps_gt), None, T(np.arange(g.n)), T(thresh.astype(np.float32)),
+                                camera="panorama")
     got = got.cpu().numpy()
     print(f"depth filter: counts {np.bincount(got.astype(int).ravel())}, {int(tie.sum())} pixels excluded as ties, "
           f"{int((got != want)[tie].sum())} of them differ")
@@ -264,7 +265,7 @@ def test_iproj_sphere(name):
     g, _, _ = R.case(name)
     c2w = se3.se3_inv(g.poses.astype(np.float64)).astype(np.float32)
     want = R.iproj(c2w, g.disps)
-    got = slam_ext.iproj_sphere(T(c2w), T(g.disps)).cpu().numpy()
+    got = slam_ext.iproj(T(c2w), T(g.disps), None, camera="panorama").cpu().numpy()
     # float32 rounding: the ray, the rotation and the sum are known to a few eps of |b| + |t| d, then divided by d
     scale = (1.0 + np.linalg.norm(c2w[:, :3], axis=-1)[:, None, None] * g.disps) / g.disps
     ratio = float((np.abs(got - want).max(-1) / (EPS32 * scale)).max())

@@ -87,10 +87,16 @@ def update_finish(coords1, dw, mask, target, weight, eta, du, damping):
                                    E, n_src, ht, wd, stream_ptr(coords1)), "update_finish")
 
 
-def _check_camera_options(camera, optimize_intrinsics):
-    """The argument errors the library answers with VIPE_EINVAL, raised before anything touches the device."""
+def _camera_code(camera):
+    """VIPE_CAM_* of a camera name; the one place an unknown name is rejected."""
     if camera not in CAMERA_CODE:
         raise ValueError(f"unknown camera {camera!r} (one of {sorted(CAMERA_CODE)})")
+    return CAMERA_CODE[camera]
+
+
+def _check_camera_options(camera, optimize_intrinsics):
+    """The argument errors the library answers with VIPE_EINVAL, raised before anything touches the device."""
+    _camera_code(camera)
     if camera == "panorama" and optimize_intrinsics:
         raise ValueError("the panorama camera has no intrinsics: optimize_intrinsics cannot be combined with it")
 
@@ -299,61 +305,43 @@ def frame_distance(poses, disps, intrinsics, pi, pj, qi, qj, di, beta):
     return dist
 
 
+def _frame_op(name, sphere_name, camera, intrinsics, intr_factor=None):
+    """A frame geometry operation for `camera`'s family -> (library call, its name in errors, its intrinsics arguments).
+    The sphere (camera="panorama") has its own entry point, which takes no intrinsics: `intrinsics` is not read and may
+    be None.  Pinhole and MEI (through the pinhole-equivalent row its caller passes) share the other; with `intr_factor`
+    the rows are full-resolution ones of either width and the call scales them itself."""
+    if _camera_code(camera) == CAMERA_CODE["panorama"]:
+        return getattr(lib(), "vipe_" + sphere_name), sphere_name, ()
+    check_gpu_contig(intrinsics)
+    scale = () if intr_factor is None else (int(intrinsics.shape[1]), float(intr_factor))
+    return getattr(lib(), "vipe_" + name), name, (ptr(intrinsics), *scale)
+
+
 def frame_distance_rig(poses, rig, disps, intrinsics, pi, qi, pj, qj, beta, bidirectional=True, intr_factor=8.0,
                        camera="pinhole"):
     """[fused] buffer.py:550-593 in one launch: poses [N,7], rig [V,7], disps [N*V,ht,wd], intrinsics [V,4|5] at full
     resolution, (pi, qi) -> (pj, qj) [M] int64 -> dist [M] (`vipe_frame_distance_rig`).  camera="panorama": the same on the
     sphere (`vipe_frame_distance_sphere`: flow in pixels of the grid, wrapped at the seam); `intrinsics` is not read."""
-    if camera not in CAMERA_CODE:
-        raise ValueError(f"unknown camera {camera!r} (one of {sorted(CAMERA_CODE)})")
+    call, what, intr = _frame_op("frame_distance_rig", "frame_distance_sphere", camera, intrinsics, intr_factor)
+    check_gpu_contig(poses, rig, disps, pi, qi, pj, qj)
     M = pi.shape[0]
     _, ht, wd = disps.shape
-    if camera == "panorama":
-        check_gpu_contig(poses, rig, disps, pi, qi, pj, qj)
-        dist = torch.empty(M, dtype=torch.float32, device=poses.device)
-        check(lib().vipe_frame_distance_sphere(ptr(poses), ptr(rig), ptr(disps), ptr(_i64(pi)), ptr(_i64(qi)), ptr(_i64(pj)),
-                                               ptr(_i64(qj)), ptr(dist), M, int(rig.shape[0]), ht, wd, float(beta),
-                                               int(bool(bidirectional)), stream_ptr(poses)), "frame_distance_sphere")
-        return dist
-    check_gpu_contig(poses, rig, disps, intrinsics, pi, qi, pj, qj)
     dist = torch.empty(M, dtype=torch.float32, device=poses.device)
-    check(lib().vipe_frame_distance_rig(ptr(poses), ptr(rig), ptr(disps), ptr(intrinsics), int(intrinsics.shape[1]),
-                                        float(intr_factor), ptr(_i64(pi)), ptr(_i64(qi)), ptr(_i64(pj)), ptr(_i64(qj)), ptr(dist),
-                                        M, int(rig.shape[0]), ht, wd, float(beta), int(bool(bidirectional)), stream_ptr(poses)),
-          "frame_distance_rig")
+    check(call(ptr(poses), ptr(rig), ptr(disps), *intr, ptr(_i64(pi)), ptr(_i64(qi)), ptr(_i64(pj)), ptr(_i64(qj)), ptr(dist),
+               M, int(rig.shape[0]), ht, wd, float(beta), int(bool(bidirectional)), stream_ptr(poses)), what)
     return dist
 
 
-def depth_filter(poses, disps, intrinsics, ix, thresh):
-    """geom_kernels.cu:1462-1486 -> counter [num,ht,wd] float32."""
-    check_gpu_contig(poses, disps, intrinsics, ix, thresh)
-    n, ht, wd = disps.shape
-    num = ix.shape[0]
-    counter = torch.zeros((num, ht, wd), dtype=torch.float32, device=poses.device)
-    check(lib().vipe_depth_filter(ptr(poses), ptr(disps), ptr(intrinsics), ptr(_i64(ix)), ptr(thresh), ptr(counter), n,
-                                  num, ht, wd, stream_ptr(poses)), "depth_filter")
-    return counter
-
-
-def depth_filter_sphere(poses, disps, ix, thresh):
-    """`depth_filter` for the panorama camera (`vipe_depth_filter_sphere`): disps are inverse ranges, the neighbour's four
-    bilinear neighbours wrap at the seam -> counter [num,ht,wd] float32."""
+def depth_filter(poses, disps, intrinsics, ix, thresh, camera="pinhole"):
+    """geom_kernels.cu:1462-1486 -> counter [num,ht,wd] float32.  camera="panorama" (`vipe_depth_filter_sphere`): disps are
+    inverse ranges, the neighbour's four bilinear neighbours wrap at the seam; `intrinsics` is not read."""
+    call, what, intr = _frame_op("depth_filter", "depth_filter_sphere", camera, intrinsics)
     check_gpu_contig(poses, disps, ix, thresh)
     n, ht, wd = disps.shape
     num = ix.shape[0]
     counter = torch.zeros((num, ht, wd), dtype=torch.float32, device=poses.device)
-    check(lib().vipe_depth_filter_sphere(ptr(poses), ptr(disps), ptr(_i64(ix)), ptr(thresh), ptr(counter), n, num, ht, wd,
-                                         stream_ptr(poses)), "depth_filter_sphere")
+    check(call(ptr(poses), ptr(disps), *intr, ptr(_i64(ix)), ptr(thresh), ptr(counter), n, num, ht, wd, stream_ptr(poses)), what)
     return counter
-
-
-def iproj_sphere(poses, disps):
-    """`iproj` for the panorama camera (`vipe_iproj_sphere`): act(pose, (ray, d)) / d -> points [n,ht,wd,3]."""
-    check_gpu_contig(poses, disps)
-    n, ht, wd = disps.shape
-    pts = torch.zeros((n, ht, wd, 3), dtype=torch.float32, device=poses.device)
-    check(lib().vipe_iproj_sphere(ptr(poses), ptr(disps), ptr(pts), n, ht, wd, stream_ptr(poses)), "iproj_sphere")
-    return pts
 
 
 def projmap(poses, disps, intrinsics, ii, jj):
@@ -368,12 +356,14 @@ def projmap(poses, disps, intrinsics, ii, jj):
     return [coords, valid]
 
 
-def iproj(poses, disps, intrinsics):
-    """geom_kernels.cu:1488-1507 -> points [n,ht,wd,3]."""
-    check_gpu_contig(poses, disps, intrinsics)
+def iproj(poses, disps, intrinsics, camera="pinhole"):
+    """geom_kernels.cu:1488-1507 -> points [n,ht,wd,3].  camera="panorama" (`vipe_iproj_sphere`): act(pose, (ray, d)) / d;
+    `intrinsics` is not read."""
+    call, what, intr = _frame_op("iproj", "iproj_sphere", camera, intrinsics)
+    check_gpu_contig(poses, disps)
     n, ht, wd = disps.shape
     pts = torch.zeros((n, ht, wd, 3), dtype=torch.float32, device=poses.device)
-    check(lib().vipe_iproj(ptr(poses), ptr(disps), ptr(intrinsics), ptr(pts), n, ht, wd, stream_ptr(poses)), "iproj")
+    check(call(ptr(poses), ptr(disps), *intr, ptr(pts), n, ht, wd, stream_ptr(poses)), what)
     return pts
 
 

@@ -343,27 +343,20 @@ class GraphBuffer:
         c2w = SE3(self.poses[t_range]).inv()
         images = self.images[t_range][..., 3::8, 3::8].permute(0, 1, 3, 4, 2)
         pts_list, mask_list = [], []
+        # the kernels' view of the camera: nothing on the sphere (rays, inverse range; the seam wraps in the filter), the
+        # 1/8-scale pinhole(-equivalent) rows otherwise
+        intr8_kernel = None if self.camera_type == "panorama" else self._pinhole_intrinsics_8()
         for v in range(self.n_views):
             c2w_view = c2w * SE3(self.rig[v])[None]
             disps_v = self.disps[t_range, v].contiguous()
-            if self.camera_type == "panorama":  # rays of the sphere, inverse range; the seam wraps in the filter
+            intr8_v = None if intr8_kernel is None else intr8_kernel[v].contiguous()
+            if self.camera_type != "mei":
                 ident = SE3.Identity(n, device=self.device).data.contiguous()
-                pts = slam_ext.iproj_sphere(ident if is_local else c2w_view.data.contiguous(), disps_v)
-                thresh_v = filter_thresh * (1.0 / disps_v.mean().item())
-                count = slam_ext.depth_filter_sphere(c2w_view.inv().data.contiguous(), disps_v,
-                                                     torch.arange(n, device=self.device),
-                                                     torch.full((n,), thresh_v, device=self.device))
-                masks = ((count >= min(2, n - 1)) & (disps_v > 0.5 * disps_v.mean(dim=[1, 2], keepdim=True))
-                         & (~self.masks[t_range, v]))
-                pts_list.append(pts)
-                mask_list.append(masks)
-                continue
-            intr8 = self.intrinsics[v].clone()
-            intr8[:4] = intr8[:4] / 8.0
-            ident = SE3.Identity(n, device=self.device).data.contiguous()
-            if self.camera_type == "pinhole":
-                pts = slam_ext.iproj(ident if is_local else c2w_view.data.contiguous(), disps_v, intr8[:4].contiguous())
+                pts = slam_ext.iproj(ident if is_local else c2w_view.data.contiguous(), disps_v, intr8_v,
+                                     camera=self.camera_type)
             else:  # MEI unprojection (cameras.py:228-250), then the same transform and dehomogenisation
+                intr8 = self.intrinsics[v].clone()
+                intr8[:4] = intr8[:4] / 8.0
                 ht, wd = disps_v.shape[1:]
                 yy, xx = torch.meshgrid(torch.arange(ht, device=self.device).float(),
                                         torch.arange(wd, device=self.device).float(), indexing="ij")
@@ -377,10 +370,9 @@ class GraphBuffer:
                     p4 = c2w_view[:, None, None].act(p4.contiguous())
                 pts = p4[..., :3] / p4[..., 3:]
             thresh_v = filter_thresh * (1.0 / disps_v.mean().item())
-            count = slam_ext.depth_filter(c2w_view.inv().data.contiguous(), disps_v,
-                                          self._pinhole_intrinsics_8()[v].contiguous(),
+            count = slam_ext.depth_filter(c2w_view.inv().data.contiguous(), disps_v, intr8_v,
                                           torch.arange(n, device=self.device),
-                                          torch.full((n,), thresh_v, device=self.device))
+                                          torch.full((n,), thresh_v, device=self.device), camera=self.camera_type)
             masks = ((count >= min(2, n - 1)) & (disps_v > 0.5 * disps_v.mean(dim=[1, 2], keepdim=True))
                      & (~self.masks[t_range, v]))
             pts_list.append(pts)
