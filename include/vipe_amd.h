@@ -102,6 +102,17 @@ int vipe_corr_lookup_conv1x1(const void* const* h_levels, const float* d_coords,
                              const float* d_bias, void* d_out, int out_ctot, int out_coff, int B, int h1, int w1,
                              int h2, int w2, int Cout, int act, const int* d_slots, int layout, void* stream);
 
+/* [fused] the same with its launch chosen by the caller; vipe_corr_lookup_conv1x1 is this with (0, 0).  The kernel runs
+ * as persistent workgroups that each take half a compute unit (registers and LDS).
+ * share_cu 0: two per compute unit, for a launch that has the device to itself.  share_cu 1: at most one becomes
+ * resident per compute unit, so that kernels of another stream run in the other half while the lookup waits on memory
+ * (vipe_update_operator with a side stream).  max_workgroups > 0 caps the grid (each workgroup then walks more pixel
+ * groups); 0: no cap.  The output does not depend on either. */
+int vipe_corr_lookup_conv1x1_ex(const void* const* h_levels, const float* d_coords, const void* d_w_packed,
+                                const float* d_bias, void* d_out, int out_ctot, int out_coff, int B, int h1, int w1,
+                                int h2, int w2, int Cout, int act, const int* d_slots, int layout, void* stream,
+                                int max_workgroups, int share_cu);
+
 /* [fused] CorrBlock.corr + pyramid (droid_net.py:56-69,94-102): volume = (f1/4)^T (f2/4) on MFMA (fp16 in,
  * fp32 accumulate, stored as dtype), then 2x2 average pooling of the target dims for levels 1..num_levels-1.
  * fmap1, fmap2 [B,C,h,w] f16; h_levels: host array of num_levels device pointers (outputs). C % 32 == 0. */

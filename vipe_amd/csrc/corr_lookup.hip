@@ -196,28 +196,49 @@ struct PyrLayout {
 
 struct RowPair { uint4v lo, hi; };
 
+// Where those two chunks live and whether each is inside the map.  The address of a chunk outside the map is that of the
+// nearest chunk inside it (nearest row, nearest chunk of the row): always readable, and in a line that the other chunk
+// of the pair or a neighbouring lane's row fetches anyway, unless the whole window is outside.
+struct RowChunks {
+  const uint4v* p[2];
+  bool ok[2];
+};
+
 template <bool BLK>
-__device__ __forceinline__ RowPair gather_row(const void* base, const PyrLayout<BLK>& lay, int l, int64_t slot, int pc,
-                                              int y1, int c0) {
+__device__ __forceinline__ RowChunks row_chunks(const void* base, const PyrLayout<BLK>& lay, int l, int64_t slot, int pc,
+                                                int y1, int c0) {
   const half_t* lvl = reinterpret_cast<const half_t*>(base);
   const int h2l = lay.h2 >> l, w2l = lay.w2 >> l;
   // 8-column pieces of a row: whole ones in the reference layout; in the blocked layout the last one may be partial
   // (columns >= w2l stored as zero by the build kernel)
   const int nchunks = BLK ? (w2l + 7) >> 3 : w2l >> 3;
   const bool rowok = (y1 >= 0) & (y1 < h2l);
-  const int yr = rowok ? y1 : 0;
+  const int yr = min(max(y1, 0), h2l - 1);
   // one slab per source pixel (reference layout; levels 2 / 3 of the blocked layout, padded): the row's chunks are
-  // contiguous and its address is formed before the bounds tests.  Levels 0 / 1 of the blocked layout are tiled
+  // contiguous.  Levels 0 / 1 of the blocked layout are tiled
   const bool tiled = BLK && l < 2;
   const uint4v* rowp = nullptr;
   if (!tiled) {
     const BlockedDims::Slab s = BLK ? lay.d.slab23(l, slot, pc) : BlockedDims::Slab{(slot * lay.P + pc) * ((int64_t)h2l * w2l), h2l, w2l};
     rowp = reinterpret_cast<const uint4v*>(lvl + s.base + (int64_t)yr * s.pitch);
   }
-  auto piece = [&](int c) { return tiled ? *reinterpret_cast<const uint4v*>(lvl + lay.d.piece01(l, slot, pc, yr, c)) : rowp[c]; };
+  RowChunks ch;
+#pragma unroll
+  for (int k = 0; k < 2; ++k) {
+    ch.ok[k] = rowok & (c0 + k >= 0) & (c0 + k < nchunks);
+    const int c = min(max(c0 + k, 0), nchunks - 1);
+    ch.p[k] = tiled ? reinterpret_cast<const uint4v*>(lvl + lay.d.piece01(l, slot, pc, yr, c)) : rowp + c;
+  }
+  return ch;
+}
+
+template <bool BLK>
+__device__ __forceinline__ RowPair gather_row(const void* base, const PyrLayout<BLK>& lay, int l, int64_t slot, int pc,
+                                              int y1, int c0) {
+  const RowChunks ch = row_chunks(base, lay, l, slot, pc, y1, c0);
   RowPair r = {uint4v{0, 0, 0, 0}, uint4v{0, 0, 0, 0}};
-  if (rowok & (c0 >= 0) & (c0 < nchunks)) r.lo = piece(c0);
-  if (rowok & (c0 + 1 >= 0) & (c0 + 1 < nchunks)) r.hi = piece(c0 + 1);
+  if (ch.ok[0]) r.lo = *ch.p[0];
+  if (ch.ok[1]) r.hi = *ch.p[1];
   return r;
 }
 
@@ -292,32 +313,37 @@ __global__ __launch_bounds__(256) void corr_pyramid_lookup_rows_kernel(LevelPtrs
 // 437 MB of HBM writes for 339 MB of output at E = 276).  Same taps, weights and addition chains as above.
 constexpr int LK4_PITCH = 208;  // halves per staged pixel (16-byte aligned rows)
 
-// Tap row j of all 4 levels of source pixel pc (coords c) -> channels 0..195 of row pl of `stage` (PITCH halves per
-// pixel).  Two phases: first all 8 loads of the lane, then the arithmetic - interleaved, each level's loads would wait
-// behind the previous level's arithmetic.
+// Tap row j of level l of one source pixel, its two chunks in r (zero outside the map) -> channels 49 l .. 49 l + 48 of row
+// pl of `stage` (PITCH halves per pixel)
+template <int PITCH>
+__device__ __forceinline__ void level_to_lds(const RowPair& r, const Taps<half_t, 3>& t, int l, int j, half_t* __restrict__ stage,
+                                             int pl) {
+  constexpr int RD = 7;
+  const auto [w00, w01, w10, w11] = t.weights();
+  const unsigned d[8] = {r.lo[0], r.lo[1], r.lo[2], r.lo[3], r.hi[0], r.hi[1], r.hi[2], r.hi[3]};
+  half2v o[4];
+  row_outputs_pk(d, t.sh(), w00, w01, w10, w11, o);
+  if (j < RD) {
+#pragma unroll
+    for (int a = 0; a < RD; ++a) stage[pl * PITCH + l * (RD * RD) + a * RD + j] = o[a >> 1][a & 1];
+  }
+}
+
+// Tap row j of all 4 levels of source pixel pc (coords c) -> channels 0..195 of row pl of `stage`.  Two phases: first all 8
+// loads of the lane, then the arithmetic - interleaved, each level's loads would wait behind the previous level's
+// arithmetic.
 template <int PITCH, bool BLK>
 __device__ __forceinline__ void lookup4_to_lds(const LevelPtrs& lv, const PyrLayout<BLK>& lay, int64_t slot, int pc, float2 c,
                                                int j, half_t* __restrict__ stage, int pl) {
-  constexpr int R = 3, RD = 7, L = 4;
-  uint4v lo[L], hi[L];
+  constexpr int R = 3, L = 4;
+  RowPair r[L];
 #pragma unroll
   for (int l = 0; l < L; ++l) {
     const Taps<half_t, R> t(c.x, c.y, l);
-    const RowPair r = gather_row(lv.p[l], lay, l, slot, pc, t.by + j, t.bx >> 3);
-    lo[l] = r.lo, hi[l] = r.hi;
+    r[l] = gather_row(lv.p[l], lay, l, slot, pc, t.by + j, t.bx >> 3);
   }
 #pragma unroll
-  for (int l = 0; l < L; ++l) {
-    const Taps<half_t, R> t(c.x, c.y, l);
-    const auto [w00, w01, w10, w11] = t.weights();
-    const unsigned d[8] = {lo[l][0], lo[l][1], lo[l][2], lo[l][3], hi[l][0], hi[l][1], hi[l][2], hi[l][3]};
-    half2v o[4];
-    row_outputs_pk(d, t.sh(), w00, w01, w10, w11, o);
-    if (j < RD) {
-#pragma unroll
-      for (int a = 0; a < RD; ++a) stage[pl * PITCH + l * (RD * RD) + a * RD + j] = o[a >> 1][a & 1];
-    }
-  }
+  for (int l = 0; l < L; ++l) level_to_lds<PITCH>(r[l], Taps<half_t, R>(c.x, c.y, l), l, j, stage, pl);
 }
 
 __global__ __launch_bounds__(256) void corr_pyramid_lookup_rows4_kernel(LevelPtrs lv, const float* __restrict__ coords,
@@ -348,93 +374,136 @@ __global__ __launch_bounds__(256) void corr_pyramid_lookup_rows4_kernel(LevelPtr
 }
 
 // ---- lookup fused with the correlation encoder's 1x1 convolution (droid_net.py:436-437 first layer, 196 -> Cout,
-// + bias + activation): the 196 looked-up channels of 32 pixels are staged in LDS as above and consumed right there
+// + bias + activation): the 196 looked-up channels of 64 pixels are staged in LDS as above and consumed right there
 // as the B operand of v_mfma_f32_16x16x32_f16; the [E,h,w,200] intermediate (339 MB written and read back per update
-// at E = 276) never exists.  Persistent workgroups: each wave keeps its 32 output channels x 224 k of the packed
-// weights in registers (loaded once), so only the gather and the 256-byte output rows touch memory.
+// at E = 276) never exists.  Persistent 512-thread workgroups: each wave keeps its 16 output channels x 224 k of the
+// packed weights in registers (loaded once), so only the gather and the 256-byte output rows touch memory.
+//
+// The kernel is bound by the gather (HBM), so what it must do is keep loads in flight, and what it must not do is hold
+// more of a CU than that takes: one workgroup is 2 waves per SIMD at <= 128 VGPRs and 47 KB of LDS, i.e. half a CU, and
+// the other half is free for a neighbour on another stream (the flow encoder in vipe_update_operator).  A lane's two
+// 16-byte row loads of level l of group g + 1 are issued as soon as the arithmetic of level l of group g has freed their
+// registers, and stay in flight through the other levels' arithmetic, the barriers, the MFMAs and the stores: each level
+// is waited for with a counted vmcnt that leaves the three younger levels out (48 to 64 KiB per workgroup in flight at
+// any time, in one register set).  The coordinate and slot loads that head the address chain of group g + 2 are issued
+// one pass earlier still.  Prefetches past the last group are clamped to it: no out-of-range address, and the loop
+// condition is uniform, so no wave leaves before a barrier.
 constexpr int LKC_PITCH = 232;   // halves per staged pixel: 224 k + 8 (row stride 464 B spreads the 16-lane b128 reads)
 constexpr int LKC_OPITCH = 136;  // halves per staged output pixel (128 couts + 8)
+constexpr int LKC_PX = 64;       // pixels per pass: 8 lanes each
+constexpr int LKC_THREADS = 8 * LKC_PX;
+constexpr int LKC_LDS = LKC_PX * (LKC_PITCH + LKC_OPITCH) * (int)sizeof(half_t);  // staged rows + staged outputs: 47,104 B
+// Asked for instead of LKC_LDS when the CU is to be shared: more than half of the 160 KiB, so a second workgroup of this
+// kernel never becomes resident on the CU, and the 76 KiB left hold a tile-convolution workgroup (76,800 B)
+constexpr int LKC_LDS_SHARED_CU = 84 * 1024;
 
 typedef _Float16 half8v __attribute__((ext_vector_type(8)));
 typedef _Float16 half4v __attribute__((ext_vector_type(4)));
 typedef float float4v __attribute__((ext_vector_type(4)));
 
 template <bool BLK>  // BLK: levels in VIPE_PYRAMID_BLOCKED (padded grid), else the reference layout
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) void corr_lookup_conv_kernel(
+__global__ __launch_bounds__(LKC_THREADS) __attribute__((amdgpu_waves_per_eu(4, 4))) void corr_lookup_conv_kernel(
     LevelPtrs lv, const float* __restrict__ coords, const half_t* __restrict__ wpk, const float* __restrict__ bias,
     half_t* __restrict__ out, int out_ctot, int out_coff, int h1, int w1, int h2, int w2, int B, int cout_pad, int act,
     const int* __restrict__ slots) {
   constexpr int RD = 7, L = 4;
-  __shared__ __align__(16) half_t stage[32 * LKC_PITCH];
-  __shared__ __align__(16) half_t ostage[32 * LKC_OPITCH];
+  extern __shared__ __align__(16) unsigned char lkc_lds[];
+  half_t* const stage = reinterpret_cast<half_t*>(lkc_lds);
+  half_t* const ostage = stage + LKC_PX * LKC_PITCH;
   const int P = h1 * w1;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int j = tid & 7, pl = tid >> 3;
   const int l16 = lane & 15, kg = lane >> 4;
-  const int gpp = (P + 31) / 32;
+  const int gpp = (P + LKC_PX - 1) / LKC_PX;
   const int ngroups = B * gpp;
   const PyrLayout<BLK> lay(P, h2, w2);
-  // this wave's weights: couts 32 wave + 16 i + l16, k = 32 s + 8 kg .. + 7  (packed [k / 64][cout_pad][64])
-  half8v af[2][7];
+  // this wave's weights: couts 16 wave + l16, k = 32 s + 8 kg .. + 7  (packed [k / 64][cout_pad][64])
+  half8v af[7];
 #pragma unroll
-  for (int i = 0; i < 2; ++i)
-#pragma unroll
-    for (int s = 0; s < 7; ++s) {
-      const int k = 32 * s + 8 * kg, r = 32 * wave + 16 * i + l16;
-      af[i][s] = *reinterpret_cast<const half8v*>(wpk + ((int64_t)(k >> 6) * cout_pad + r) * 64 + (k & 63));
-    }
-  float4 bv[2];
-#pragma unroll
-  for (int i = 0; i < 2; ++i) bv[i] = *reinterpret_cast<const float4*>(bias + 32 * wave + 16 * i + 4 * kg);
+  for (int s = 0; s < 7; ++s) {
+    const int k = 32 * s + 8 * kg, r = 16 * wave + l16;
+    af[s] = *reinterpret_cast<const half8v*>(wpk + ((int64_t)(k >> 6) * cout_pad + r) * 64 + (k & 63));
+  }
+  const float4 bv = *reinterpret_cast<const float4*>(bias + 16 * wave + 4 * kg);
   // zero the k padding of the staged rows once (columns 196..231 are never written by the lookup)
   zero_channels(stage + pl * LKC_PITCH, L * RD * RD, LKC_PITCH, j, 8);
 
-  for (int grp = blockIdx.x; grp < ngroups; grp += gridDim.x) {
-    const int n = grp / gpp, p = (grp % gpp) * 32 + pl;
-    const bool pok = p < P;
-    const int pc = pok ? p : P - 1;
-    const float2 c = reinterpret_cast<const float2*>(coords)[(int64_t)n * P + pc];
-    const int ns = slots ? slots[n] : n;  // pooled pyramids: edge n lives in slot slots[n] of the level buffers
-    lookup4_to_lds<LKC_PITCH>(lv, lay, ns, pc, c, j, stage, pl);
+  // head of a group's address chain, for this lane's pixel: coordinates and pyramid slot.  Groups past the last one
+  // read the last one's
+  struct Head { float2 c; int ns, pc; };
+  auto head = [&](int grp) {
+    grp = min(grp, ngroups - 1);
+    const int n = grp / gpp;
+    Head hd;
+    hd.pc = min((grp % gpp) * LKC_PX + pl, P - 1);
+    hd.c = reinterpret_cast<const float2*>(coords)[(int64_t)n * P + hd.pc];
+    hd.ns = slots ? slots[n] : n;  // pooled pyramids: edge n lives in slot slots[n] of the level buffers
+    return hd;
+  };
+  const int step = gridDim.x;
+  Head hd0 = head(blockIdx.x), hd1 = head(blockIdx.x + step);
+  // this lane's two chunks of level l for a group, as loaded (what lies outside the map is dropped when they are used):
+  // loads under no branch, so that the waits below are counted ones and leave the younger loads in flight
+  auto issue = [&](const Head& hd, int l) {
+    const Taps<half_t, 3> t(hd.c.x, hd.c.y, l);
+    const RowChunks ch = row_chunks(lv.p[l], lay, l, hd.ns, hd.pc, t.by + j, t.bx >> 3);
+    return RowPair{*ch.p[0], *ch.p[1]};
+  };
+  RowPair rows[L];
+#pragma unroll
+  for (int l = 0; l < L; ++l) {
+    rows[l] = issue(hd0, l);
+    // in the order in which the loop issues them: where the two orders differ, the loop's first wait (for level 0, with
+    // the other levels left in flight) is counted for the worse of them and drains every level
+    __builtin_amdgcn_sched_barrier(0);
+  }
+
+  for (int grp = blockIdx.x; grp < ngroups; grp += step) {
+    const Head hd2 = head(grp + 2 * step);
+    // level by level: this group's arithmetic, then the next group's loads into the registers it has just freed
+#pragma unroll
+    for (int l = 0; l < L; ++l) {
+      const Taps<half_t, 3> t(hd0.c.x, hd0.c.y, l);
+      const RowChunks ch = row_chunks(lv.p[l], lay, l, hd0.ns, hd0.pc, t.by + j, t.bx >> 3);  // for ok[] only
+      const uint4v zero = {0, 0, 0, 0};
+      level_to_lds<LKC_PITCH>(RowPair{ch.ok[0] ? rows[l].lo : zero, ch.ok[1] ? rows[l].hi : zero}, t, l, j, stage, pl);
+      rows[l] = issue(hd1, l);
+    }
     __syncthreads();
-    // ---- 1x1 convolution of the 32 staged pixels: D[cout, pixel]
-    float4v acc[2][2];
+    // ---- 1x1 convolution of the 64 staged pixels: D[cout, pixel], four 16-pixel tiles per wave
+    float4v acc[4];
 #pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-      for (int jj = 0; jj < 2; ++jj) acc[i][jj] = float4v{0.f, 0.f, 0.f, 0.f};
+    for (int jj = 0; jj < 4; ++jj) acc[jj] = float4v{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
     for (int s = 0; s < 7; ++s)
 #pragma unroll
-      for (int jj = 0; jj < 2; ++jj) {
+      for (int jj = 0; jj < 4; ++jj) {
         const half8v xf = *reinterpret_cast<const half8v*>(stage + (16 * jj + l16) * LKC_PITCH + 32 * s + 8 * kg);
-#pragma unroll
-        for (int i = 0; i < 2; ++i) acc[i][jj] = __builtin_amdgcn_mfma_f32_16x16x32_f16(af[i][s], xf, acc[i][jj], 0, 0, 0);
+        acc[jj] = __builtin_amdgcn_mfma_f32_16x16x32_f16(af[s], xf, acc[jj], 0, 0, 0);
       }
 #pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-      for (int jj = 0; jj < 2; ++jj) {
-        half4v hv;
-        const float v0 = acc[i][jj][0] + bv[i].x, v1 = acc[i][jj][1] + bv[i].y;
-        const float v2 = acc[i][jj][2] + bv[i].z, v3 = acc[i][jj][3] + bv[i].w;
-        hv[0] = (half_t)(act == VIPE_ACT_RELU ? fmaxf(v0, 0.0f) : v0);
-        hv[1] = (half_t)(act == VIPE_ACT_RELU ? fmaxf(v1, 0.0f) : v1);
-        hv[2] = (half_t)(act == VIPE_ACT_RELU ? fmaxf(v2, 0.0f) : v2);
-        hv[3] = (half_t)(act == VIPE_ACT_RELU ? fmaxf(v3, 0.0f) : v3);
-        *reinterpret_cast<half4v*>(ostage + (16 * jj + l16) * LKC_OPITCH + 32 * wave + 16 * i + 4 * kg) = hv;
-      }
+    for (int jj = 0; jj < 4; ++jj) {
+      half4v hv;
+      const float v0 = acc[jj][0] + bv.x, v1 = acc[jj][1] + bv.y, v2 = acc[jj][2] + bv.z, v3 = acc[jj][3] + bv.w;
+      hv[0] = (half_t)(act == VIPE_ACT_RELU ? fmaxf(v0, 0.0f) : v0);
+      hv[1] = (half_t)(act == VIPE_ACT_RELU ? fmaxf(v1, 0.0f) : v1);
+      hv[2] = (half_t)(act == VIPE_ACT_RELU ? fmaxf(v2, 0.0f) : v2);
+      hv[3] = (half_t)(act == VIPE_ACT_RELU ? fmaxf(v3, 0.0f) : v3);
+      *reinterpret_cast<half4v*>(ostage + (16 * jj + l16) * LKC_OPITCH + 16 * wave + 4 * kg) = hv;
+    }
     __syncthreads();
-    // 256 contiguous bytes per pixel: 2 x 16 B per thread
+    // 256 contiguous bytes per pixel: 2 x 16 B per thread.  The next pass writes `stage` behind this barrier and `ostage`
+    // behind its own first one
     {
-      const int pq = tid >> 3, ck = tid & 7;
-      const int pg = (grp % gpp) * 32 + pq;
+      const int n = grp / gpp, ck = tid & 7;
+      const int pg = (grp % gpp) * LKC_PX + pl;
       if (pg < P) {
         half_t* dst = out + ((int64_t)n * P + pg) * out_ctot + out_coff;
-        *reinterpret_cast<uint4v*>(dst + ck * 8) = *reinterpret_cast<const uint4v*>(ostage + pq * LKC_OPITCH + ck * 8);
-        *reinterpret_cast<uint4v*>(dst + 64 + ck * 8) = *reinterpret_cast<const uint4v*>(ostage + pq * LKC_OPITCH + 64 + ck * 8);
+        *reinterpret_cast<uint4v*>(dst + ck * 8) = *reinterpret_cast<const uint4v*>(ostage + pl * LKC_OPITCH + ck * 8);
+        *reinterpret_cast<uint4v*>(dst + 64 + ck * 8) = *reinterpret_cast<const uint4v*>(ostage + pl * LKC_OPITCH + 64 + ck * 8);
       }
     }
+    hd0 = hd1, hd1 = hd2;
   }
 }
 
@@ -578,11 +647,31 @@ VIPE_EXPORT int vipe_corr_pyramid_lookup_nhwc(const void* const* h_levels, const
                              stream);
 }
 
+// compute units of the current device (0: the query failed), asked once per device
+static int device_compute_units() {
+  static std::atomic<int> cus[64];
+  int d = 0;
+  (void)hipGetDevice(&d);
+  int n = cus[d & 63].load(std::memory_order_relaxed);
+  if (n > 0) return n;
+  if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, d) != hipSuccess || n <= 0) return 0;
+  cus[d & 63].store(n, std::memory_order_relaxed);
+  return n;
+}
+
 VIPE_EXPORT int vipe_corr_lookup_conv1x1(const void* const* h_levels, const float* d_coords, const void* d_w_packed,
                                          const float* d_bias, void* d_out, int out_ctot, int out_coff, int B, int h1,
                                          int w1, int h2, int w2, int Cout, int act, const int* d_slots, int layout,
                                          void* stream) {
-  VIPE_CHECK_ARG(B >= 0 && h1 > 0 && w1 > 0 && h2 > 0 && w2 > 0);
+  return vipe_corr_lookup_conv1x1_ex(h_levels, d_coords, d_w_packed, d_bias, d_out, out_ctot, out_coff, B, h1, w1, h2, w2,
+                                     Cout, act, d_slots, layout, stream, 0, 0);
+}
+
+VIPE_EXPORT int vipe_corr_lookup_conv1x1_ex(const void* const* h_levels, const float* d_coords, const void* d_w_packed,
+                                            const float* d_bias, void* d_out, int out_ctot, int out_coff, int B, int h1,
+                                            int w1, int h2, int w2, int Cout, int act, const int* d_slots, int layout,
+                                            void* stream, int max_workgroups, int share_cu) {
+  VIPE_CHECK_ARG(B >= 0 && h1 > 0 && w1 > 0 && h2 > 0 && w2 > 0 && max_workgroups >= 0);
   if (B == 0) return VIPE_OK;
   VIPE_CHECK_ARG(h_levels && d_coords && d_w_packed && d_bias && d_out);
   VIPE_CHECK_ARG(act == VIPE_ACT_NONE || act == VIPE_ACT_RELU);
@@ -598,11 +687,21 @@ VIPE_EXPORT int vipe_corr_lookup_conv1x1(const void* const* h_levels, const floa
     VIPE_CHECK_ARG(h_levels[i]);
     lv.p[i] = h_levels[i];
   }
-  const int64_t ngroups = (int64_t)B * ((h1 * w1 + 31) / 32);
-  const int blocks = (int)std::min<int64_t>(ngroups, 256 * 4);
+  const int64_t ngroups = (int64_t)B * ((h1 * w1 + LKC_PX - 1) / LKC_PX);
+  VIPE_CHECK_ARG(ngroups < (1 << 30));  // the kernel indexes groups, and two prefetch steps past them, in int
+  // persistent workgroups, each half a CU (see the kernel): two per CU when the kernel has the device to itself, one -
+  // enforced by the LDS request, which grid size alone would not - when a neighbour on another stream is to run beside it
+  const int cus = device_compute_units();
+  if (cus <= 0) return VIPE_EINVAL;
+  int64_t blocks = std::min<int64_t>(ngroups, share_cu ? cus : 2 * cus);
+  if (max_workgroups > 0) blocks = std::min<int64_t>(blocks, max_workgroups);
+  const size_t lds = share_cu ? LKC_LDS_SHARED_CU : LKC_LDS;
   auto launch = [&](auto blk) {
-    corr_lookup_conv_kernel<decltype(blk)::value><<<blocks, 256, 0, as_stream(stream)>>>(
-        lv, d_coords, (const half_t*)d_w_packed, d_bias, (half_t*)d_out, out_ctot, out_coff, h1, w1, h2, w2, B, 128, act, d_slots);
+    auto* kernel = corr_lookup_conv_kernel<decltype(blk)::value>;
+    static std::atomic<uint64_t> seen{0};  // one per layout: each call of the generic lambda instantiates its own
+    vipe_once_per_device(seen, [&] { (void)hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, LKC_LDS_SHARED_CU); });
+    kernel<<<(int)blocks, LKC_THREADS, lds, as_stream(stream)>>>(lv, d_coords, (const half_t*)d_w_packed, d_bias, (half_t*)d_out,
+                                                                 out_ctot, out_coff, h1, w1, h2, w2, B, 128, act, d_slots);
   };
   if (layout == VIPE_PYRAMID_BLOCKED) launch(std::true_type{});
   else launch(std::false_type{});

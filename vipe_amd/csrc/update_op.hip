@@ -86,8 +86,9 @@ VIPE_EXPORT int vipe_update_operator(const vipe_update_weights* wt, const vipe_u
   FORK(0);
   // encoders (droid_net.py:481-482)
   if (b->levels[0]) {
-    RUN(vipe_corr_lookup_conv1x1(b->levels, b->coords, wt->corr0_w, wt->corr0_b, b->c1, 128, 0, E, H, W, b->h2, b->w2, 128,
-                                 VIPE_ACT_RELU, b->slots, b->pyramid_layout, stream));
+    // with a side stream the lookup leaves half of every CU to the flow encoder
+    RUN(vipe_corr_lookup_conv1x1_ex(b->levels, b->coords, wt->corr0_w, wt->corr0_b, b->c1, 128, 0, E, H, W, b->h2, b->w2, 128,
+                                    VIPE_ACT_RELU, b->slots, b->pyramid_layout, stream, 0, s2 ? 1 : 0));
   } else {
     VIPE_CHECK_ARG(b->corr);
     RUN(vipe_conv2d_fused(b->corr, 200, 0, nullptr, 0, 0, 200, wt->corr0_w, wt->corr0_b, nullptr, 0, 0, b->c1, 128, 0, nullptr,

@@ -280,13 +280,16 @@ def corr_pyramid_lookup_nhwc(levels, coords, radius=3, channel_stride=200):
     return out
 
 
-def corr_lookup_conv1x1(levels, coords, w_packed, bias, out, out_coff=0, cout=128, act="relu", slots=None, grid=None):
+def corr_lookup_conv1x1(levels, coords, w_packed, bias, out, out_coff=0, cout=128, act="relu", slots=None, grid=None,
+                        max_workgroups=0, share_cu=False):
     """[fused] `CorrBlock.__call__` (4 levels, radius 3) + the correlation encoder's first 1x1 convolution
     (droid_net.py:436-437): writes out[E,h,w,C] channels [out_coff, out_coff + cout) without materialising the
     196-channel lookup.  levels: fp16 pyramid of `corr_pyramid_build` (reference layout) or of
     `corr_pyramid_build_indexed` (blocked layout: 7-D level 0; `grid` = (h, w) of the targets, needed when the store is
     padded); coords [E,h,w,2] f32.  w_packed / bias: the buffers of an `update_engine._Packed` (the bias readable up to
     the padded output-channel count, as the header asks).
+    share_cu: at most one half-CU workgroup per compute unit, for a launch that has a neighbour on another stream
+    (default: two, the whole CU); max_workgroups > 0 caps the grid.  Neither changes a bit of the output.
     Raises NotImplementedError for configurations the fused kernel does not cover (callers fall back to
     `corr_pyramid_lookup_nhwc` + the conv)."""
     check_gpu_contig(coords, out, *levels)
@@ -306,9 +309,10 @@ def corr_lookup_conv1x1(levels, coords, w_packed, bias, out, out_coff=0, cout=12
     require(tuple(coords.shape) == (E, h1, w1, 2) and tuple(out.shape[:3]) == (E, h1, w1) and out.dtype == torch.float16,
             "bad coords / out shape")
     arr = (ctypes.c_void_p * 4)(*[lv.data_ptr() for lv in levels])
-    check(lib().vipe_corr_lookup_conv1x1(ctypes.cast(arr, ctypes.c_void_p), ptr(coords), ptr(w_packed), ptr(bias), ptr(out),
-                                         out.shape[-1], out_coff, E, h1, w1, h2, w2, cout, {"none": 0, "relu": 1}[act],
-                                         ptr(slots) if slots is not None else None, layout, stream_ptr(coords)),
+    check(lib().vipe_corr_lookup_conv1x1_ex(ctypes.cast(arr, ctypes.c_void_p), ptr(coords), ptr(w_packed), ptr(bias), ptr(out),
+                                            out.shape[-1], out_coff, E, h1, w1, h2, w2, cout, {"none": 0, "relu": 1}[act],
+                                            ptr(slots) if slots is not None else None, layout, stream_ptr(coords),
+                                            int(max_workgroups), int(bool(share_cu))),
           "corr_lookup_conv1x1")
     return out
 
