@@ -715,6 +715,29 @@ int vipe_convex_upsample(const void* d_mask, int mask_dtype, const float* d_data
                          int N, int R, int h, int w, int C, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Per-frame depth export: the inverse of vipe_frame_ingest's geometry.  An addition: the reference takes per-frame depth
+ * from monocular depth networks; here it is the reciprocal of the SLAM disparities, back at the frame's native size.
+ * ------------------------------------------------------------------------------------------- */
+/* out[n] [H0,W0] is made from d_disp[d_rows[n]] [H,W] (d_rows NULL: from d_disp[n], then N <= R): the map is put back at
+ * rows [top, top + H), columns [left, left + W) of the resized frame (h1,w1), the band the centre crop removed taking the
+ * edge row / column (replicate padding), resampled to (H0,W0) as F.interpolate(mode="bilinear", align_corners=False)
+ * does, and inverted.  Per axis, with n_res = h1 | w1, n_out = H0 | W0, off = top | left, n_in = H | W:
+ *   scale = float(n_res) / float(n_out);  src = max(fma(scale, dst + 0.5, -0.5), 0)  (one fused operation, as in
+ *   vipe_frame_ingest);  src = clamp(src - off, 0, n_in - 1);  i0 = int(src), i1 = min(i0 + 1, n_in - 1), l1 = src - i0,
+ *   l0 = 1 - l1
+ *   d = ly0 * (lx0 * a + lx1 * b) + ly1 * (lx0 * c + lx1 * e), every product and sum rounded on its own
+ *   depth = d > 0 ? depth_scale / d : 0, one correctly rounded division; out_dtype VIPE_F16 stores its
+ *   round-to-nearest-even
+ * With H0 = h1 = H, W0 = w1 = W, top = left = 0 the map is the identity: out = depth_scale / disp exactly.
+ *   d_disp [R,H,W] f32;  d_rows [N] int64 or NULL - an entry outside [0, R) leaves out[n] unwritten;
+ *   d_out  [N,H0,W0], out_dtype VIPE_F32 or VIPE_F16
+ * Sizes must be positive, top, left >= 0, top + H <= h1, left + W <= w1, N <= 65535 and ceil(H0 / 4) <= 65535 (grid
+ * limits), pointers non-null unless N == 0 (then VIPE_OK, no launch); anything else is VIPE_EINVAL.  One output pixel per
+ * thread in 64 x 4 tiles, the batch index in grid.z. */
+int vipe_depth_export(const float* d_disp, const int64_t* d_rows, void* d_out, int out_dtype, int N, int R, int H, int W,
+                      int h1, int w1, int top, int left, int H0, int W0, float depth_scale, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Sparse keypoint tracker: corner detection and pyramidal Lucas-Kanade (klt_track.hip), the producer of the tracks
  * that `SparseTracks` feeds to the motion filter and to the BA's second flow term.  An addition: the reference's only
  * real tracker wraps a closed CUDA package.  tests/klt_reference.py restates this arithmetic in float64.

@@ -71,6 +71,38 @@ def save_depth_artifacts(path, depths, inds=None):
             z.writestr(f"{frame_idx:05d}.exr", write_exr_half(d))
 
 
+class DepthZipWriter:
+    """`save_depth_artifacts` one map at a time: the archive is opened once and every call writes one
+    `<frame_idx:05d>.exr` - usable as `SLAMConfig.frame_depth_sink`, so that a long clip's native-size maps leave the
+    device as pass 2's chunks complete (each call copies its map to the host).  One archive holds one view's maps (the
+    reference writes one `depth/<name>.zip` per stream): calls for other views than `view_idx` are ignored.  Close it
+    (or use it as a context manager) before reading the file."""
+
+    def __init__(self, path, view_idx=0):
+        os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+        self.view_idx, self.count = view_idx, 0
+        self._zip = zipfile.ZipFile(path, "w", zipfile.ZIP_DEFLATED)
+
+    def __call__(self, frame_idx, view_idx, depth):
+        from .exr import write_exr_half
+        if view_idx != self.view_idx:
+            return
+        d = depth.detach().cpu().numpy() if torch.is_tensor(depth) else np.asarray(depth)
+        self._zip.writestr(f"{int(frame_idx):05d}.exr", write_exr_half(d))
+        self.count += 1
+
+    def close(self):
+        if self._zip is not None:
+            self._zip.close()
+            self._zip = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+
 def read_depth_artifacts(path):
     """io.py:279-310 -> iterator of (frame_idx, float32 [H,W] tensor); an unreadable member yields an all-NaN map of the
     last good size, as the reference does"""

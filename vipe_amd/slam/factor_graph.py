@@ -204,6 +204,10 @@ class FactorGraph:
     # full resolution with THIS iteration's mask into `buffer.disps_up` (DROID-SLAM's order; `_upsample_disps`).  Needs
     # `GraphBuffer(upsample_disps=True)`.  Off: not one launch, allocation or argument differs.
     upsample = False
+    # With `upsample`: None - every source row of the graph is upsampled (the keyframe graphs).  A flattened buffer row
+    # (slot * V): only source rows from there on are, the rows before it are left as they are - pass 2's graph, whose
+    # sources include keyframes whose `disps_up` rows are the global BA's result and must not be rewritten.
+    upsample_from_row = None
     _last_ba = None  # t0, t1, damping and flags of the last BA `update` / `update_batch` issued (`marginals`' defaults)
 
     def __init__(self, update_module, buffer, device, max_factors=48, incremental=True, cross_view=False):
@@ -509,15 +513,30 @@ class FactorGraph:
         self.target_inac, self.weight_inac = cap[0][:, :n + k], cap[1][:, :n + k]
         return cap[0], cap[1], n
 
-    def _upsample_disps(self, mask, du):
+    def _upsample_disps(self, mask, du, own=None):
         """mask [n_src,h,w,576] f16 of the operator (row s belongs to source slot du[s], as `eta` does in update_finish)
         -> buffer.disps_up[du] = convex upsampling of buffer.disps[du], read and written in place through the flattened
-        (frame * V + view) rows: no gathers.  `droid_net_ext.cvx_upsample` is the only route to the kernel."""
+        (frame * V + view) rows: no gathers.  `droid_net_ext.cvx_upsample` is the only route to the kernel.
+        `own` = (rows, keep) of `_own_rows`: the kernel skips the mask rows whose entry of `rows` is -1, and only the
+        rows with `keep` set are flagged."""
         from ..ext import droid_net_ext
         buf = self.buffer
         require(buf.disps_up is not None, "FactorGraph.upsample needs GraphBuffer(upsample_disps=True)")
-        droid_net_ext.cvx_upsample(buf.flattened_disps[..., None], mask, rows=du, out=buf.flattened_disps_up[..., None])
-        buf.disps_up_valid.view(-1)[du] = True
+        droid_net_ext.cvx_upsample(buf.flattened_disps[..., None], mask, rows=du if own is None else own[0],
+                                   out=buf.flattened_disps_up[..., None])
+        flags = buf.disps_up_valid.view(-1)
+        if own is None:
+            flags[du] = True
+        else:  # no boolean-mask indexing: that would read the count back
+            flags[du] = flags[du] | own[1]
+
+    def _own_rows(self, P):
+        """`upsample_from_row`: (P["du"] with the rows before it mapped to -1, which rows are kept), once per edge plan"""
+        key = ("own_rows", int(self.upsample_from_row))
+        if key not in P:
+            keep = P["du"] >= key[1]
+            P[key] = (torch.where(keep, P["du"], torch.full_like(P["du"], -1)), keep)
+        return P[key]
 
     def _shift_plan(self, plan5, base):
         """(pi, qi, di, pj, qj) -> the same relative to keyframe `base` (+ base), see GraphBuffer.bundle_adjustment"""
@@ -634,7 +653,10 @@ class FactorGraph:
         buf.bundle_adjustment(target.view(E, -1, 2), weight.view(E, -1, 2), self.damping, ii, jj, n_iters=itrs,
                               **self._last_ba, plan=plan, ba_state=self._ba_state, plan_key=plan_key, overlap=ba_overlap)
         if self.upsample:  # after the BA: this iteration's mask on the disparities it has just produced
-            self._upsample_disps(upmask, P["du"])
+            if self.upsample_from_row is None:
+                self._upsample_disps(upmask, P["du"])
+            else:
+                self._upsample_disps(upmask, P["du"], own=self._own_rows(P))
         if overlap:
             main.wait_stream(self._side)
             self._gate_state = gate_state

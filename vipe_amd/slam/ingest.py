@@ -7,6 +7,8 @@ vipe/streams/base.py:164-254), intrinsics rescaled on the way in and recovered t
     ingest_frames(frames, ..)  one `vipe_frame_ingest` launch per view: the native frame is read once and everything
                                `_precompute_features` / `_add_keyframe` need is written - images, the encoders'
                                normalised fp16 input, the 1/8 invalid mask, the sensor disparities
+    depth_export(disp, ..)     the way back (`vipe_depth_export`): SLAM-resolution disparity maps through the inverse of
+                               that crop and resize to the native size, as depth
 
 Decoding stays with the caller: frames arrive as tensors.  The nearest-neighbour `instance` channel of `VideoFrame` is
 not read by the SLAM path and is not carried."""
@@ -84,6 +86,47 @@ def frame_ingest(rgb, resize, images, x4, mask=None, mask8=None, depth=None, dis
     check(lib().vipe_frame_ingest(ptr(rgb), _RGB_CODE[rgb.dtype], ptr(mask), ptr(depth), H0, W0, h1, w1, top, left, H, W,
                                   ptr(images), ptr(x4), ptr(mask8) if mask is not None else None,
                                   ptr(disps_sens) if depth is not None else None, stream_ptr(rgb)), "vipe_frame_ingest")
+
+
+def export_params(resize_or_params, H, W):
+    """-> (h1, w1, top, left, H0, W0) of `vipe_depth_export` for maps of H x W: from a `StandardResize` (whose
+    `out_size` must be that size), from such a tuple as it is, or - None - the identity"""
+    r = resize_or_params
+    if r is None:
+        return (H, W, 0, 0, H, W)
+    if isinstance(r, StandardResize):
+        require(r.out_size == (H, W), f"the maps are {H} x {W}, the resize's out_size is {r.out_size}")
+        return (*r.size, r.crop[0], r.crop[2], *r.native_size)
+    p = tuple(int(v) for v in r)
+    require(len(p) == 6, "export parameters: (h1, w1, top, left, H0, W0)")
+    return p
+
+
+def depth_export(disp, resize_or_params, rows=None, out=None, dtype=torch.float16, depth_scale=1.0):
+    """Disparity maps at SLAM resolution -> depth maps at the frames' native size, one `vipe_depth_export` launch: the
+    inverse of `frame_ingest`'s geometry (the cropped band replicate-padded back, bilinear resample with
+    align_corners=False, in the disparity domain), then depth = depth_scale / d where d > 0 and 0 elsewhere.
+
+    disp [R,H,W] fp32; `resize_or_params` a `StandardResize` with out_size (H, W), a tuple (h1, w1, top, left, H0, W0)
+    or None for the identity (H0 = H, W0 = W: exactly depth_scale / disp); rows int64 [N] or None (N = R, out[n] from
+    disp[n]): out[n] is made from disp[rows[n]], entries outside [0, R) leave out[n] as it is; out [N,H0,W0] fp16 / fp32
+    (fresh and zero-filled, of `dtype`, when None).  Device tensors only.  The single route from Python to the kernel."""
+    if not disp.is_cuda:
+        raise NotImplementedError("depth_export: device tensors only (vipe_depth_export is a HIP kernel)")
+    require(disp.dim() == 3 and disp.dtype == torch.float32 and disp.is_contiguous(), "disp: contiguous [R,H,W] fp32")
+    R, H, W = (int(v) for v in disp.shape)
+    h1, w1, top, left, H0, W0 = export_params(resize_or_params, H, W)
+    if rows is not None:
+        require(rows.is_cuda and rows.device == disp.device and rows.dtype == torch.int64 and rows.dim() == 1
+                and rows.is_contiguous(), "rows: contiguous int64 [N] on disp's device")
+    N = R if rows is None else int(rows.shape[0])
+    if out is None:
+        out = torch.zeros((N, H0, W0), dtype=dtype, device=disp.device)
+    require(out.is_cuda and out.device == disp.device and out.is_contiguous() and tuple(out.shape) == (N, H0, W0)
+            and out.dtype in (torch.float16, torch.float32), f"out: contiguous [{N},{H0},{W0}] fp16 / fp32 on disp's device")
+    check(lib().vipe_depth_export(ptr(disp), ptr(rows), ptr(out), F16 if out.dtype == torch.float16 else F32, N, R, H, W,
+                                  h1, w1, top, left, H0, W0, float(depth_scale), stream_ptr(disp)), "vipe_depth_export")
+    return out
 
 
 def ingest_frames(frames, resize, device):

@@ -2,8 +2,8 @@
 (vipe/slam/components/inner_filler.py:46-138), the second pass of `SLAMSystem.run` (system.py:284-294): every frame of the
 video is appended behind the keyframes, in chunks of `infill_chunk_size`; a chunk's poses start from the constant-velocity
 interpolation between its neighbouring keyframes and are refined by ten update iterations on a graph of (keyframe ->
-frame) edges - motion only (`motion_only=True, limited_disp=True`) unless `infill_dense_disp`.  The buffer's frame
-count returns to the keyframes after every chunk."""
+frame) edges - motion only (`motion_only=True, limited_disp=True`) unless `infill_dense_disp`, which adds the (frame ->
+keyframe) edges and frees the chunk's disparities.  The buffer's frame count returns to the keyframes after every chunk."""
 from dataclasses import dataclass
 
 import torch
@@ -36,6 +36,12 @@ class InnerFiller:
         self.net, self.video, self.args, self.device = update_module, video, args, device
         self.start_idx = -1
         self.filled_poses, self.filled_dense_disps = [], []
+        # `SLAMConfig.frame_depth` (not in the reference): the LAST of a chunk's ten updates also upsamples the chunk's own
+        # rows to full resolution (`FactorGraph.upsample_from_row`: `buffer.disps_up[start_idx:n_frames]`, with the mask of
+        # that update, after its BA).  Needs `infill_dense_disp` - without it the chunk's frames are no source of any
+        # edge and have no mask - and `GraphBuffer(upsample_disps=True)`.  The rows are the caller's to read before the
+        # next chunk reuses the slots, and the `disps_up_valid` flags its to clear.
+        self.upsample_own_rows = False
 
     def set_start_idx(self, start_idx):
         self.start_idx = int(start_idx)
@@ -76,7 +82,11 @@ class InnerFiller:
         if self.args.infill_dense_disp:
             graph.add_factors(infill_inds, t0)
             graph.add_factors(infill_inds, t1)
-        for _ in range(10):
+        if self.upsample_own_rows:
+            assert self.args.infill_dense_disp, "the chunk's frames have upsampling masks only as sources of dense edges"
+        for it in range(10):
+            if self.upsample_own_rows and it == 9:
+                graph.upsample, graph.upsample_from_row = True, s * v.n_views
             graph.update(s, total, motion_only=not self.args.infill_dense_disp, limited_disp=True)
         self.filled_poses.append(SE3(v.poses[s:total].clone()))
         if self.args.infill_dense_disp:

@@ -82,6 +82,14 @@ def rescale_marginals(disp_var, pose_cov, s):
     return disp_var / (s * s), pose_cov * (d[:, None] * d[None, :])
 
 
+def rescale_frame_depths(frame_depths, s):
+    """`SLAMOutput.frame_depths` (or one map of a `frame_depth_sink`) of a result that is rescaled by the metric-depth
+    factor `s` the way `FilledReturn.scale` does it (disparities / s, translations * s): depths * s.  `run` itself
+    applies no metric rescaling, so the maps are in the trajectory's units until this is applied.  -> a new tensor of
+    the same dtype (fp16 maps are scaled in fp32 and rounded once)."""
+    return (frame_depths.float() * s).to(frame_depths.dtype)
+
+
 class SLAMOutput:
     """interface.py:143-163: what `SLAMSystem.run` returns - trajectory (camera -> world per frame, SE3 [N]), intrinsics
     [V,4], the rig, the map, the BA residual.
@@ -95,10 +103,20 @@ class SLAMOutput:
     `keyframe_pose_cov` [N_kf,6,6] f64 (left tangent of the world -> camera keyframe pose, X <- Exp(dx) X, order
     translation, rotation), aligned with `keyframe_ids`: marginal covariances of the last global BA's damped, weighted
     linear system - the network's confidence weights act as inverse variances, without a noise scale, so they rank how
-    well pixels and poses are determined rather than give metric error bars.  NaN where not free (the gauge keyframe)."""
+    well pixels and poses are determined rather than give metric error bars.  NaN where not free (the gauge keyframe).
+
+    None unless `SLAMConfig.frame_depth`: `frame_depths` [T,V,H0,W0] (`SLAMConfig.frame_depth_dtype`, fp16 by default),
+    one depth map per frame and view of the video - the reciprocal of the frame's full-resolution disparity (a
+    keyframe's from the global BA, every other frame's from pass 2), for `run(..., native_resolution=True)` at the
+    frames' native size, otherwise at SLAM resolution; 0 where the disparity is not positive; in the trajectory's units
+    (`rescale_frame_depths` for a metric factor).  For the panorama camera the disparities are inverse ranges, so the
+    maps are ranges.  It stays None when a `SLAMConfig.frame_depth_sink` took the maps instead.  `frame_disps_lowres`
+    [T,V,h,w] f32: pass 2's disparities of every frame at the BA's 1/8 grid (`FilledReturn.dense_disps`)."""
 
     def __init__(self, *, trajectory, intrinsics, rig=None, slam_map=None, ba_residual=0.0, keyframe_disps_up=None,
-                 keyframe_disps_up_valid=None, keyframe_disp_var=None, keyframe_pose_cov=None):
+                 keyframe_disps_up_valid=None, keyframe_disp_var=None, keyframe_pose_cov=None, frame_depths=None,
+                 frame_disps_lowres=None):
+        self.frame_depths, self.frame_disps_lowres = frame_depths, frame_disps_lowres
         self.keyframe_disp_var, self.keyframe_pose_cov = keyframe_disp_var, keyframe_pose_cov
         self.trajectory, self.intrinsics, self.rig, self.slam_map, self.ba_residual = trajectory, intrinsics, rig, slam_map, ba_residual
         self.keyframe_disps_up, self.keyframe_disps_up_valid = keyframe_disps_up, keyframe_disps_up_valid

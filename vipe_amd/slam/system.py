@@ -13,10 +13,11 @@ the monocular depth networks / sparse tracks / the rerun visualisation are outsi
             (`MotionFilter.prefetch` / `check`); same decisions, same results, the filter fills the chip the frontend's
             single-workgroup solves leave idle
             `SLAMBackend.run(7)`, `SLAMBackend.run(backend_iters)` (system.py:279-282)
-    pass 2  every frame appended again behind the keyframes, `InnerFiller` in chunks (system.py:284-294)
+    pass 2  every frame appended again behind the keyframes, `InnerFiller` in chunks (system.py:284-294); with
+            `SLAMConfig.frame_depth` (an addition) every chunk leaves as depth maps at the frames' native size
             `extract_slam_map`, `SLAMOutput(trajectory = filled poses inverted, intrinsics, rig, map)` (system.py:303-316)
 """
-from dataclasses import dataclass, field
+from dataclasses import dataclass, field, replace
 
 import torch
 
@@ -54,6 +55,16 @@ class SLAMConfig:
     disp_uncertainty: bool = False  # marginal covariances of the last global BA (`SLAMOutput.keyframe_disp_var` /
                                     # `keyframe_pose_cov`): one `FactorGraph.marginals` call per clip after the last backend
                                     # pass, with that pass's BA arguments.  Off: nothing is allocated, no launch differs
+    frame_depth: bool = False      # one depth map per FRAME and view (`SLAMOutput.frame_depths`): the buffer gets
+                                   # `disps_up` and the keyframe graphs upsample as with `upsample_disps`; pass 2 runs with
+                                   # `infill_dense_disp` forced on - that changes it from motion-only to poses AND
+                                   # disparities of every frame - and upsamples each chunk's own rows after the last of
+                                   # its ten BAs; one `vipe_depth_export` launch per chunk takes them (a keyframe's frame
+                                   # takes the keyframe's row) to the native size as depth.  Off: nothing changes
+    frame_depth_dtype: torch.dtype = torch.float16   # of `frame_depths` / the sink's maps (float16 or float32)
+    frame_depth_sink: object = None  # callable (frame_idx, view_idx, depth [H0,W0] device tensor), called in frame order
+                                     # as pass 2's chunks complete (`driver.artifacts.DepthZipWriter`); `frame_depths`
+                                     # then stays None: a long clip does not hold T native-size maps on the device
     sparse_tracks: str = None      # "klt": `run` builds a `KLTSparseTracks(n_views)` (corners + pyramidal Lucas-Kanade in
                                    # HIP) when the caller passed no tracker - the motion filter's track score and the BA's
                                    # track term get real tracks.  None: no tracker is built, nothing is launched or changed
@@ -92,16 +103,23 @@ class SLAMSystem:
         c = self.config
         self.buffer = GraphBuffer(height, width, n_views=n_views, buffer_size=c.buffer, init_disp=c.init_disp,
                                   cross_view_idx=c.cross_view_idx, camera_type=camera_type, device=self.device,
-                                  **({"upsample_disps": True} if c.upsample_disps else {}))
+                                  **({"upsample_disps": True} if c.upsample_disps or c.frame_depth else {}))
         self.buffer.rig[:] = rig.data.to(self.device)
         self.buffer.sparse_tracks = self.sparse_tracks
         self.motion_filter = self.motion_filter_cls(self.droid_net, sparse_tracks=self.sparse_tracks, thresh=c.filter_thresh,
                                                     device=self.device)
         self.frontend = SLAMFrontend(self.droid_net.update, self.buffer, c.frontend, self.device)
         self.backend = SLAMBackend(self.droid_net.update, self.buffer, c.backend, self.device)
-        self.inner_filler = InnerFiller(self.droid_net.update, self.buffer, c.infill, self.device)
-        if c.upsample_disps:  # the keyframe graphs; InnerFiller's stays off (non-keyframe depth is not upsampled)
+        infill = c.infill
+        if c.frame_depth:  # every frame needs a disparity map of its own: pass 2 is no longer motion-only
+            assert c.frame_depth_dtype in (torch.float16, torch.float32), "SLAMConfig.frame_depth_dtype: float16 or float32"
+            infill = replace(c.infill, infill_dense_disp=True)
+        self.inner_filler = InnerFiller(self.droid_net.update, self.buffer, infill, self.device)
+        if c.upsample_disps or c.frame_depth:  # the keyframe graphs: their rows are final after the global BA
             self.frontend.graph.upsample = self.backend.upsample = True
+        # InnerFiller's graph stays off under `upsample_disps` alone; with `frame_depth` it upsamples the chunk's own
+        # rows - the slots behind the keyframes - in the last of its ten updates
+        self.inner_filler.upsample_own_rows = bool(c.frame_depth)
         if self.metric_depth is not None:
             assert n_views == 1, "the global scale lies in the null space of a multi-view problem (system.py:115-118)"
         self.backend.depth_model = self.metric_depth
@@ -241,6 +259,15 @@ class SLAMSystem:
         # in ONE batched call (per image the same arithmetic; instance norm is per image): 39 launches per chunk instead of
         # 39 per frame, and at 16 images the encoder kernels fill the chip
         chunk = max(1, int(self.config.infill.infill_chunk_size))
+        pending = []  # frames appended since the last `compute`, in slot order
+        kf_slot = None
+        self.frame_depths = None
+        if self.config.frame_depth:  # keyframe timestamp -> slot: one read-back per clip
+            kf_slot = {int(t): k for k, t in enumerate(b.tstamp[:b.n_frames].tolist())}
+            if self.config.frame_depth_sink is None:
+                size = self._resizes[0].native_size if native else (b.height, b.width)
+                self.frame_depths = torch.empty((total, b.n_views) + tuple(size), dtype=self.config.frame_depth_dtype,
+                                                device=self.device)
         for c0 in range(0, total, chunk):
             idx = range(c0, min(c0 + chunk, total))
             pre = [self._features(frames[i]) for i in idx]
@@ -256,10 +283,37 @@ class SLAMSystem:
             for j, i in enumerate(idx):
                 self._add_keyframe(i, pre[j][0], pre[j][1], frames[i], phase=2, reuse=feats[j] if feats else None,
                                    x4=pre[j][2], disps_sens=pre[j][3])
+                pending.append(i)
                 if self.inner_filler.check() or i == total - 1:
                     self.inner_filler.compute()
+                    if kf_slot is not None:  # the chunk's rows are valid until the next chunk reuses the slots
+                        self._export_frame_depths(pending, kf_slot)
+                    pending = []
         mark("pass2_done_seconds")
         self.work["total"] = {k: _fg.WORK[k] - work0[k] for k in work0}
+
+    def _export_frame_depths(self, frame_ids, kf_slot):
+        """`SLAMConfig.frame_depth`, right after `InnerFiller.compute` of the chunk `frame_ids` (consecutive frame indices,
+        in the slots behind the keyframes): ONE `vipe_depth_export` launch (the views share one frame size, hence one
+        `StandardResize`) turns `buffer.disps_up` rows into depth at the native size - of a frame that is a keyframe the
+        KEYFRAME's row, the global BA's result (in pass 2 such a frame has only a zero-baseline edge to itself and one
+        neighbour), of every other frame its own pass-2 row - into `frame_depths[frame_ids]` or, map by map in frame
+        order, to the sink.  The chunk's `disps_up_valid` flags are cleared again: the slots belong to the next chunk."""
+        from .._lib import upload
+        from .ingest import depth_export
+        b, c = self.buffer, self.config
+        s, V, n = b.n_frames, b.n_views, len(frame_ids)  # `compute` has set n_frames back to the keyframes
+        rows = upload([(kf_slot.get(f, s + j)) * V + v for j, f in enumerate(frame_ids) for v in range(V)], self.device)
+        out = None
+        if self.frame_depths is not None:
+            out = self.frame_depths[frame_ids[0]:frame_ids[0] + n].view(n * V, *self.frame_depths.shape[2:])
+        out = depth_export(b.flattened_disps_up, self._resizes[0] if self._resizes is not None else None, rows=rows,
+                           out=out, dtype=c.frame_depth_dtype)
+        b.disps_up_valid[s:s + n] = False
+        if c.frame_depth_sink is not None:
+            for j, f in enumerate(frame_ids):
+                for v in range(V):
+                    c.frame_depth_sink(f, v, out[j * V + v])
 
     def _check_camera(self, camera_type, frames, native_resolution):
         """What a camera model rules out, before anything is built or touches the device.  The panorama
@@ -313,7 +367,15 @@ class SLAMSystem:
         `keyframe_pose_cov` [N_kf,6,6]: marginal covariances of the last global BA's damped, weighted linear system at the
         final keyframe state (`GraphBuffer.ba_marginals`), NaN where a frame / pose was not free (the gauge keyframe's
         pose).  `run` applies no metric rescaling; a caller that rescales the result by a factor s (disparities / s,
-        translations * s) passes the two fields through `interface.rescale_marginals`."""
+        translations * s) passes the two fields through `interface.rescale_marginals`.
+
+        With `SLAMConfig.frame_depth` it carries `frame_depths` [T,V,H0,W0] (`frame_depth_dtype`, fp16 by default): one
+        depth map per frame and view, at the native size with native_resolution=True and at SLAM resolution otherwise - or
+        hands every map to `SLAMConfig.frame_depth_sink` as pass 2's chunks complete and leaves the field None - and
+        `frame_disps_lowres` [T,V,h,w], pass 2's 1/8-grid disparities.  Depth is the reciprocal of the camera model's
+        disparity: for camera_type="panorama" the maps are RANGES along the ray, not z.  This changes pass 2 from
+        motion-only to poses and disparities (`infill_dense_disp` forced on), and `keyframe_disps_up` comes with it.  Units
+        are the trajectory's; no metric rescaling here (`interface.rescale_frame_depths`)."""
         frames = [f if isinstance(f, (list, tuple)) else [f] for f in frames]
         total, n_views = len(frames), len(frames[0])
         assert total > 0 and all(len(f) == n_views for f in frames)
@@ -364,4 +426,7 @@ class SLAMSystem:
             disp_var, pose_cov = self.marginals
             up.update(keyframe_disp_var=disp_var[:n_kf * V].view(n_kf, V, *disp_var.shape[1:]).clone(),
                       keyframe_pose_cov=pose_cov[:n_kf].clone())
+        if self.config.frame_depth:
+            up.update(frame_depths=self.frame_depths, frame_disps_lowres=filled.dense_disps)
+            self.frame_depths = None
         return SLAMOutput(trajectory=filled.poses.inv(), intrinsics=intrinsics, rig=SE3(b.rig.clone()), slam_map=slam_map, **up)
