@@ -737,6 +737,34 @@ int vipe_convex_upsample(const void* d_mask, int mask_dtype, const float* d_data
 int vipe_depth_export(const float* d_disp, const int64_t* d_rows, void* d_out, int out_dtype, int N, int R, int H, int W,
                       int h1, int w1, int top, int left, int H0, int W0, float depth_scale, void* stream);
 
+/* Per-frame depth confidence (depth_consistency.hip; an addition, the ABI version stays 4): for every pixel of the maps
+ * vipe_depth_export writes, how many of K neighbour rows of the same buffer see the pixel's point and how many of those
+ * confirm its disparity - the multi-view consistency count of DROID-SLAM's / the reference's depth_filter
+ * (geom_kernels.cu:678-793), at native size, relative instead of absolute, any row against any rows.
+ *   d_disp [R,H,W] f32: rows of GraphBuffer.disps_up, row r = buffer slot r / n_views, view r % n_views
+ *   d_poses [R / n_views,7] world -> camera; d_rig [n_views,7]; d_intrinsics [n_views,intr_dim] at SLAM resolution
+ *   (intr_dim 4 for VIPE_CAM_PINHOLE and VIPE_CAM_PANORAMA, whose rows are never read; 5 for VIPE_CAM_MEI)
+ *   d_rows [N] int64 or NULL (identity, then N <= R): the source row of out[n]; outside [0, R): out[n] stays unwritten
+ *   d_nbr [N,K] int64: neighbour rows of out[n]; entries outside [0, R) (-1: none) or equal to the source row are skipped
+ *   d_out [N,H0,W0] u8; (h1, w1, top, left, H0, W0) as for vipe_depth_export
+ * Per output pixel: taps and blended disparity d exactly as vipe_depth_export; d <= 0 (or not a number) gives 0.  The
+ * pixel's place in the SLAM grid is the clamped source coordinate (u, v) = (ix0 + lx1, iy0 + ly1), so the replicate-padded
+ * band repeats its edge pixel's test.  ray = iproj(intrinsics of r's view, u, v); for each neighbour q:
+ *   T = (rig[vq]^-1 G[pq]) (rig[vr]^-1 G[pr])^-1;  X1 = R ray + t d;  valid as vipe_reproject's `valid`;  (x', y') its
+ *   coordinates with q's view's intrinsics;  d' = d / X1.z (pinhole, MEI) or d / |X1| (panorama: inverse range)
+ *   x0 = floor(x'), y0 = floor(y');  visible iff valid, 0 <= y0 <= H - 2 and 0 <= x0 <= W - 2 (panorama: the columns
+ *   x0, x0 + 1 wrap modulo W instead)
+ *   agrees iff visible and one of disp[q][y0 | y0 + 1][x0 | x0 + 1] is a t > 0 with |d' - t| <= tol * d'
+ *   out = agree_count | visible_count << 4
+ * 1 <= K <= 8, 1 <= n_views <= 8, R % n_views == 0, intr_dim matching the camera, tol > 0, vipe_depth_export's size and
+ * grid conditions, for VIPE_CAM_PANORAMA the identity crop (top = left = 0, h1 = H, w1 = W: a crop breaks the sphere),
+ * pointers non-null (d_rows excepted) unless N == 0 (then VIPE_OK, no launch); anything else is VIPE_EINVAL.  One output
+ * pixel per thread in 64 x 4 tiles, the map index in grid.z; no atomics. */
+int vipe_depth_consistency(const float* d_disp, const float* d_poses, const float* d_rig, const float* d_intrinsics,
+                           int intr_dim, int camera, const int64_t* d_rows, const int64_t* d_nbr, unsigned char* d_out,
+                           int N, int K, int R, int n_views, int H, int W, int h1, int w1, int top, int left, int H0,
+                           int W0, float tol, void* stream);
+
 /* ---------------------------------------------------------------------------------------------
  * Sparse keypoint tracker: corner detection and pyramidal Lucas-Kanade (klt_track.hip), the producer of the tracks
  * that `SparseTracks` feeds to the motion filter and to the BA's second flow term.  An addition: the reference's only

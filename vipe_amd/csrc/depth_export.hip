@@ -21,11 +21,11 @@
 // wave owns 64 x-adjacent pixels of one output row: its store is 128 (f16) / 256 (f32) contiguous bytes, its four taps
 // walk two source rows front to back and come out of L1 / L2 (upsampling 384 x 512 -> 1080 x 1920, 64 output pixels
 // span 18 source pixels).  Memory bound: H*W*4 B read once, H0*W0*(2|4) B written.
-#include "common.cuh"
+#include "export_taps.cuh"
 
 namespace {
 
-constexpr int TILE_W = 64, TILE_H = 4;
+using namespace export_geom;  // TILE_W x TILE_H tiles, Tap, make_tap, blend: shared with depth_consistency.hip
 
 struct ExportArgs {
   const float* disp;    // [R,H,W]
@@ -35,27 +35,6 @@ struct ExportArgs {
   float scale_y, scale_x;  // float(h1) / float(H0), float(w1) / float(W0)
   float depth_scale;
 };
-
-struct Tap {
-  int i0, i1;
-  float l0, l1;
-};
-
-__device__ __forceinline__ Tap make_tap(int dst, float scale, int off, int in) {
-  float src = __fmaf_rn(scale, (float)dst + 0.5f, -0.5f);
-  src = src < 0.0f ? 0.0f : src;
-  src = fminf(fmaxf(src - (float)off, 0.0f), (float)(in - 1));
-  Tap t;
-  t.i0 = min((int)src, in - 1);
-  t.i1 = min(t.i0 + 1, in - 1);
-  t.l1 = src - (float)t.i0;
-  t.l0 = 1.0f - t.l1;
-  return t;
-}
-
-__device__ __forceinline__ float blend(const Tap& ty, const Tap& tx, float a, float b, float c, float d) {
-  return ty.l0 * (tx.l0 * a + tx.l1 * b) + ty.l1 * (tx.l0 * c + tx.l1 * d);
-}
 
 __device__ __forceinline__ void put(float* p, float v) { *p = v; }
 __device__ __forceinline__ void put(half_t* p, float v) { *p = f2h(v); }
@@ -83,8 +62,7 @@ VIPE_EXPORT int vipe_depth_export(const float* d_disp, const int64_t* d_rows, vo
                                   int H, int W, int h1, int w1, int top, int left, int H0, int W0, float depth_scale,
                                   void* stream) {
   VIPE_CHECK_ARG(N >= 0 && R >= 0);
-  VIPE_CHECK_ARG(H > 0 && W > 0 && h1 > 0 && w1 > 0 && H0 > 0 && W0 > 0 && top >= 0 && left >= 0);
-  VIPE_CHECK_ARG((int64_t)top + H <= h1 && (int64_t)left + W <= w1);
+  VIPE_CHECK_ARG(geometry_ok(H, W, h1, w1, top, left, H0, W0));
   VIPE_CHECK_ARG(out_dtype == VIPE_F16 || out_dtype == VIPE_F32);
   VIPE_CHECK_ARG(d_rows || N <= R);
   const int by = (H0 + TILE_H - 1) / TILE_H;

@@ -9,6 +9,8 @@ vipe/streams/base.py:164-254), intrinsics rescaled on the way in and recovered t
                                normalised fp16 input, the 1/8 invalid mask, the sensor disparities
     depth_export(disp, ..)     the way back (`vipe_depth_export`): SLAM-resolution disparity maps through the inverse of
                                that crop and resize to the native size, as depth
+    depth_consistency(..)      on the same grid (`vipe_depth_consistency`): per pixel of those maps, how many neighbour
+                               rows see its point and how many confirm its disparity; `nearest_keyframes` picks the rows
 
 Decoding stays with the caller: frames arrive as tensors.  The nearest-neighbour `instance` channel of `VideoFrame` is
 not read by the SLAM path and is not carried."""
@@ -126,6 +128,65 @@ def depth_export(disp, resize_or_params, rows=None, out=None, dtype=torch.float1
             and out.dtype in (torch.float16, torch.float32), f"out: contiguous [{N},{H0},{W0}] fp16 / fp32 on disp's device")
     check(lib().vipe_depth_export(ptr(disp), ptr(rows), ptr(out), F16 if out.dtype == torch.float16 else F32, N, R, H, W,
                                   h1, w1, top, left, H0, W0, float(depth_scale), stream_ptr(disp)), "vipe_depth_export")
+    return out
+
+
+def depth_consistency(disp, poses, rig, intrinsics, camera, resize_or_params, rows, nbr, tol, out=None):
+    """Multi-view consistency count of the maps `depth_export` makes of the same `disp` and `rows`, one
+    `vipe_depth_consistency` launch: per native-size pixel, how many of its map's K neighbour rows see the pixel's point
+    (high nibble) and how many of those hold a disparity within `tol` (relative) of the one the point would have there
+    (low nibble); `interface.unpack_depth_conf` splits the byte.  0 where the blended disparity is not positive.
+
+    disp [R,H,W] fp32: rows of `GraphBuffer.flattened_disps_up`, row = slot * V + view; poses [R / V,7] world -> camera;
+    rig [V,7]; intrinsics [V,4] ([V,5] MEI) at SLAM resolution; camera "pinhole" / "mei" / "panorama" (the panorama takes
+    no crop or resize of a cropped frame: identity parameters or a pure resize); rows int64 [N] or None (out[n] from
+    disp[n]), entries outside [0, R) leave out[n] as it is; nbr int64 [N,K], 1 <= K <= 8, neighbour rows, entries
+    outside [0, R) (-1) or equal to the map's own row are skipped; out [N,H0,W0] uint8 (fresh and zero-filled when
+    None).  Device tensors only.  The single route from Python to the kernel."""
+    from .._lib import CAMERA_CODE
+    if not disp.is_cuda:
+        raise NotImplementedError("depth_consistency: device tensors only (vipe_depth_consistency is a HIP kernel)")
+    require(camera in CAMERA_CODE, f"camera: one of {sorted(CAMERA_CODE)}")
+    require(disp.dim() == 3 and disp.dtype == torch.float32 and disp.is_contiguous(), "disp: contiguous [R,H,W] fp32")
+    R, H, W = (int(v) for v in disp.shape)
+    h1, w1, top, left, H0, W0 = export_params(resize_or_params, H, W)
+    require(rig.dim() == 2 and rig.shape[1] == 7, "rig: [V,7]")
+    V = int(rig.shape[0])
+    require(1 <= V <= 8 and R % V == 0, "rig: 1 to 8 views, and disp holds whole slots (R a multiple of V)")
+    idim = 5 if camera == "mei" else 4
+    for t, shape, what in ((poses, (R // V, 7), "poses"), (rig, (V, 7), "rig"), (intrinsics, (V, idim), "intrinsics")):
+        require(t.is_cuda and t.device == disp.device and t.dtype == torch.float32 and t.is_contiguous()
+                and tuple(t.shape) == shape, f"{what}: contiguous fp32 {list(shape)} on disp's device")
+    if rows is not None:
+        require(rows.is_cuda and rows.device == disp.device and rows.dtype == torch.int64 and rows.dim() == 1
+                and rows.is_contiguous(), "rows: contiguous int64 [N] on disp's device")
+    N = R if rows is None else int(rows.shape[0])
+    require(nbr.is_cuda and nbr.device == disp.device and nbr.dtype == torch.int64 and nbr.dim() == 2 and nbr.is_contiguous()
+            and nbr.shape[0] == N and 1 <= nbr.shape[1] <= 8, f"nbr: contiguous int64 [{N},K] on disp's device, 1 <= K <= 8")
+    require(float(tol) > 0, "tol must be positive")
+    if out is None:
+        out = torch.zeros((N, H0, W0), dtype=torch.uint8, device=disp.device)
+    require(out.is_cuda and out.device == disp.device and out.is_contiguous() and tuple(out.shape) == (N, H0, W0)
+            and out.dtype == torch.uint8, f"out: contiguous [{N},{H0},{W0}] uint8 on disp's device")
+    check(lib().vipe_depth_consistency(ptr(disp), ptr(poses), ptr(rig), ptr(intrinsics), idim, CAMERA_CODE[camera], ptr(rows),
+                                       ptr(nbr), ptr(out), N, int(nbr.shape[1]), R, V, H, W, h1, w1, top, left, H0, W0,
+                                       float(tol), stream_ptr(disp)), "vipe_depth_consistency")
+    return out
+
+
+def nearest_keyframes(frame_tstamps, kf_tstamps, kf_valid, k):
+    """The neighbour rule of `SLAMConfig.frame_depth_conf`, host arithmetic: for each frame the slots of the `k` keyframes
+    nearest in time -> int64 [n, k].  Keyframes are ordered by |kt - t|, ties to the earlier one; a keyframe with kt == t
+    is left out (a frame that is a keyframe never tests against itself), so is one whose `kf_valid` entry is false (its
+    `disps_up` row is not there); short lists are padded with -1.  Slot = index into `kf_tstamps`."""
+    kts = [int(t) for t in kf_tstamps]
+    ok = [bool(v) for v in kf_valid]
+    require(len(kts) == len(ok) and k >= 1, "one validity flag per keyframe, k >= 1")
+    out = torch.full((len(frame_tstamps), k), -1, dtype=torch.int64)
+    for i, t in enumerate(int(t) for t in frame_tstamps):
+        order = sorted((abs(kt - t), kt, s) for s, kt in enumerate(kts) if ok[s] and kt != t)
+        for j, (_, _, s) in enumerate(order[:k]):
+            out[i, j] = s
     return out
 
 

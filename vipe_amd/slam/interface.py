@@ -90,6 +90,14 @@ def rescale_frame_depths(frame_depths, s):
     return (frame_depths.float() * s).to(frame_depths.dtype)
 
 
+def unpack_depth_conf(conf):
+    """`SLAMOutput.frame_depth_conf` (or one map of a `frame_depth_conf_sink`), uint8 -> (agree, visible), two uint8
+    tensors of its shape: of the pixel's neighbour keyframes, how many confirm its depth and how many see its point at
+    all (agree <= visible <= `SLAMConfig.frame_depth_conf_neighbours`).  visible == 0 says nothing either way."""
+    require(conf.dtype == torch.uint8, "depth confidence maps are uint8")
+    return conf & 15, conf >> 4
+
+
 class SLAMOutput:
     """interface.py:143-163: what `SLAMSystem.run` returns - trajectory (camera -> world per frame, SE3 [N]), intrinsics
     [V,4], the rig, the map, the BA residual.
@@ -111,12 +119,17 @@ class SLAMOutput:
     frames' native size, otherwise at SLAM resolution; 0 where the disparity is not positive; in the trajectory's units
     (`rescale_frame_depths` for a metric factor).  For the panorama camera the disparities are inverse ranges, so the
     maps are ranges.  It stays None when a `SLAMConfig.frame_depth_sink` took the maps instead.  `frame_disps_lowres`
-    [T,V,h,w] f32: pass 2's disparities of every frame at the BA's 1/8 grid (`FilledReturn.dense_disps`)."""
+    [T,V,h,w] f32: pass 2's disparities of every frame at the BA's 1/8 grid (`FilledReturn.dense_disps`).
+
+    None unless `SLAMConfig.frame_depth_conf` (and no `frame_depth_conf_sink`): `frame_depth_conf` [T,V,H0,W0] uint8,
+    pixel for pixel beside `frame_depths`: the multi-view consistency count against the frame's nearest keyframes of
+    the same view, agree | visible << 4 (`unpack_depth_conf`)."""
 
     def __init__(self, *, trajectory, intrinsics, rig=None, slam_map=None, ba_residual=0.0, keyframe_disps_up=None,
                  keyframe_disps_up_valid=None, keyframe_disp_var=None, keyframe_pose_cov=None, frame_depths=None,
-                 frame_disps_lowres=None):
+                 frame_disps_lowres=None, frame_depth_conf=None):
         self.frame_depths, self.frame_disps_lowres = frame_depths, frame_disps_lowres
+        self.frame_depth_conf = frame_depth_conf
         self.keyframe_disp_var, self.keyframe_pose_cov = keyframe_disp_var, keyframe_pose_cov
         self.trajectory, self.intrinsics, self.rig, self.slam_map, self.ba_residual = trajectory, intrinsics, rig, slam_map, ba_residual
         self.keyframe_disps_up, self.keyframe_disps_up_valid = keyframe_disps_up, keyframe_disps_up_valid

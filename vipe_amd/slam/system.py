@@ -65,6 +65,15 @@ class SLAMConfig:
     frame_depth_sink: object = None  # callable (frame_idx, view_idx, depth [H0,W0] device tensor), called in frame order
                                      # as pass 2's chunks complete (`driver.artifacts.DepthZipWriter`); `frame_depths`
                                      # then stays None: a long clip does not hold T native-size maps on the device
+    frame_depth_conf: bool = False  # beside every map of `frame_depth` a uint8 map `SLAMOutput.frame_depth_conf`:
+                                    # per pixel, how many of the frame's nearest keyframes (same view) see its point and
+                                    # how many confirm its depth; one `vipe_depth_consistency` launch per chunk, right
+                                    # after the export and on its rows.  It only reads.  Off: nothing is allocated, no
+                                    # launch differs
+    frame_depth_conf_neighbours: int = 4   # keyframes per frame (1 to 8), nearest in time (`ingest.nearest_keyframes`)
+    frame_depth_conf_tol: float = 0.05     # relative disparity (= depth) difference that still agrees; `map_filter_thresh`'s value
+    frame_depth_conf_sink: object = None   # callable (frame_idx, view_idx, conf [H0,W0] uint8 device tensor), in frame order;
+                                           # `frame_depth_conf` then stays None
     sparse_tracks: str = None      # "klt": `run` builds a `KLTSparseTracks(n_views)` (corners + pyramidal Lucas-Kanade in
                                    # HIP) when the caller passed no tracker - the motion filter's track score and the BA's
                                    # track term get real tracks.  None: no tracker is built, nothing is launched or changed
@@ -94,6 +103,11 @@ class SLAMSystem:
         self.metric_depth = depth_model  # system.py:114-127 builds it from `keyframe_depth`; here the caller's
         self.sparse_tracks = sparse_tracks
         assert self.config.sparse_tracks in (None, "klt"), "SLAMConfig.sparse_tracks: None or 'klt'"
+        if self.config.frame_depth_conf:
+            c = self.config
+            assert c.frame_depth, "SLAMConfig.frame_depth_conf rates the maps of frame_depth: set frame_depth=True as well"
+            assert 1 <= int(c.frame_depth_conf_neighbours) <= 8, "SLAMConfig.frame_depth_conf_neighbours: 1 to 8"
+            assert c.frame_depth_conf_tol > 0, "SLAMConfig.frame_depth_conf_tol must be positive"
         self._config_tracker = sparse_tracks is None and self.config.sparse_tracks == "klt"  # then a fresh one per run
         self._resizes = None  # one `StandardResize` per view inside `run(..., native_resolution=True)`, None outside it
         # system.py:91 builds a tracker from the config; here the caller's (`track_image(frames)` per frame of pass 1,
@@ -268,6 +282,12 @@ class SLAMSystem:
                 size = self._resizes[0].native_size if native else (b.height, b.width)
                 self.frame_depths = torch.empty((total, b.n_views) + tuple(size), dtype=self.config.frame_depth_dtype,
                                                 device=self.device)
+        self.frame_depth_conf = self._kf_times = None
+        if self.config.frame_depth_conf:  # the keyframes' timestamps and row flags, final from here on: one more read-back
+            self._kf_times = (b.tstamp[:b.n_frames].tolist(), b.disps_up_valid[:b.n_frames].tolist())
+            if self.config.frame_depth_conf_sink is None:
+                size = self._resizes[0].native_size if native else (b.height, b.width)
+                self.frame_depth_conf = torch.zeros((total, b.n_views) + tuple(size), dtype=torch.uint8, device=self.device)
         for c0 in range(0, total, chunk):
             idx = range(c0, min(c0 + chunk, total))
             pre = [self._features(frames[i]) for i in idx]
@@ -309,11 +329,39 @@ class SLAMSystem:
             out = self.frame_depths[frame_ids[0]:frame_ids[0] + n].view(n * V, *self.frame_depths.shape[2:])
         out = depth_export(b.flattened_disps_up, self._resizes[0] if self._resizes is not None else None, rows=rows,
                            out=out, dtype=c.frame_depth_dtype)
+        conf = self._depth_confidence(frame_ids, rows) if c.frame_depth_conf else None  # reads the rows the export read
         b.disps_up_valid[s:s + n] = False
         if c.frame_depth_sink is not None:
             for j, f in enumerate(frame_ids):
                 for v in range(V):
                     c.frame_depth_sink(f, v, out[j * V + v])
+        if conf is not None and c.frame_depth_conf_sink is not None:
+            for j, f in enumerate(frame_ids):
+                for v in range(V):
+                    c.frame_depth_conf_sink(f, v, conf[j * V + v])
+
+    def _depth_confidence(self, frame_ids, rows):
+        """`SLAMConfig.frame_depth_conf` for the chunk `_export_frame_depths` has just exported, before its slots are
+        released: ONE `vipe_depth_consistency` launch over the same `rows` (all views), each map against the rows of
+        its frame's nearest keyframes in the same view (`nearest_keyframes`: never the frame's own keyframe, never a
+        keyframe without a `disps_up` row).  Neighbours are keyframes only: their rows are final during pass 2, the
+        motion filter guarantees their baselines, and the result does not depend on how pass 2 is chunked.
+        -> conf [n*V,H0,W0] uint8, a view of `frame_depth_conf[frame_ids]` when that is kept."""
+        from .._lib import upload
+        from . import ingest
+        b, c = self.buffer, self.config
+        V, n, K = b.n_views, len(frame_ids), int(c.frame_depth_conf_neighbours)
+        kf_t, kf_ok = self._kf_times
+        nbr = torch.full((n, V, K), -1, dtype=torch.int64)
+        for v in range(V):
+            slots = ingest.nearest_keyframes(frame_ids, kf_t, [ok[v] for ok in kf_ok], K)
+            nbr[:, v] = torch.where(slots >= 0, slots * V + v, slots)
+        out = None
+        if self.frame_depth_conf is not None:
+            out = self.frame_depth_conf[frame_ids[0]:frame_ids[0] + n].view(n * V, *self.frame_depth_conf.shape[2:])
+        return ingest.depth_consistency(b.flattened_disps_up, b.poses, b.rig, b.intrinsics, b.camera_type,
+                                        self._resizes[0] if self._resizes is not None else None, rows,
+                                        upload(nbr.view(n * V, K), self.device), c.frame_depth_conf_tol, out=out)
 
     def _check_camera(self, camera_type, frames, native_resolution):
         """What a camera model rules out, before anything is built or touches the device.  The panorama
@@ -375,7 +423,13 @@ class SLAMSystem:
         `frame_disps_lowres` [T,V,h,w], pass 2's 1/8-grid disparities.  Depth is the reciprocal of the camera model's
         disparity: for camera_type="panorama" the maps are RANGES along the ray, not z.  This changes pass 2 from
         motion-only to poses and disparities (`infill_dense_disp` forced on), and `keyframe_disps_up` comes with it.  Units
-        are the trajectory's; no metric rescaling here (`interface.rescale_frame_depths`)."""
+        are the trajectory's; no metric rescaling here (`interface.rescale_frame_depths`).
+
+        With `SLAMConfig.frame_depth_conf` on top of it, `frame_depth_conf` [T,V,H0,W0] uint8 lies pixel for pixel beside
+        `frame_depths` (or every map goes to `SLAMConfig.frame_depth_conf_sink`): how many of the frame's nearest
+        keyframes of the same view see the pixel's point (high nibble) and how many of those confirm its depth within
+        `frame_depth_conf_tol` (low nibble; `interface.unpack_depth_conf`).  It only reads: depths and trajectory are
+        what they are without it."""
         frames = [f if isinstance(f, (list, tuple)) else [f] for f in frames]
         total, n_views = len(frames), len(frames[0])
         assert total > 0 and all(len(f) == n_views for f in frames)
@@ -429,4 +483,7 @@ class SLAMSystem:
         if self.config.frame_depth:
             up.update(frame_depths=self.frame_depths, frame_disps_lowres=filled.dense_disps)
             self.frame_depths = None
+        if self.config.frame_depth_conf:
+            up.update(frame_depth_conf=self.frame_depth_conf)
+            self.frame_depth_conf = None
         return SLAMOutput(trajectory=filled.poses.inv(), intrinsics=intrinsics, rig=SE3(b.rig.clone()), slam_map=slam_map, **up)
