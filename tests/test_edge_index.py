@@ -161,6 +161,89 @@ def test_update_batch_chunks_partition_the_groups_of_eight_source_frames():
     assert fg.chunk_groups(np.zeros(0, dtype=np.int64), 8) == []
 
 
+# `update_batch`'s budget arithmetic and residency rule on the 20-keyframe graph of the GPU parity test (E = 74), one
+# pyramid = 696320 bytes on the 8 x 64 grid (blocked layout 8 x 64 sources, 2 x 4 rows, 2 x 32 columns, 4 levels, fp16).
+# (V, volume GB, chunk edges, steps) -> (groups, max_edges, budget_rows, max_rows, policy, pyramids built over the passes):
+# the budget arithmetic (volume bytes against the budget, max(8, ...), max(256, budget_rows // (8 V))) and the rule "keep a chunk
+# while kept + its rows + the largest chunk's fit the budget" worked out for these inputs
+BYTES_PER_PYRAMID = 512 * 512 * 2 * (1 + 1 / 4 + 1 / 16 + 1 / 64)
+BACKEND_PLANS = [
+    ((1, 160, 4096, 1), ([[0, 8, 16]], 4096, 246723, 74, "none", 74)),
+    ((1, 160, 4096, 2), ([[0, 8, 16]], 4096, 246723, 74, "all", 74)),
+    ((1, 160, 1, 2), ([[0], [8], [16]], 8, 246723, 32, "all", 74)),
+    ((1, 0.04, 1, 2), ([[0], [8], [16]], 8, 61, 32, "some", 119)),
+    ((1, 0.04, 4096, 2), ([[0, 8], [16]], 61, 61, 61, "some", 148)),
+    ((1, 0.01, 4096, 2), ([[0], [8], [16]], 15, 15, 32, "some", 148)),
+    ((1, 0.04, 1, 1), ([[0], [8], [16]], 8, 61, 32, "none", 74)),
+    ((2, 160, 4096, 2), ([[0, 8, 16]], 4096, 246723, 148, "all", 148)),
+    ((2, 0.04, 4096, 2), ([[0], [8], [16]], 30, 61, 64, "some", 296)),
+    ((2, 0.01, 4096, 2), ([[0], [8], [16]], 8, 15, 64, "some", 296)),
+]
+
+
+def _backend_cnt():
+    from vipe_amd.synth import make_graph
+    ii = make_graph(n=20, height=64, width=512, radius=2, seed=53).ii
+    assert len(ii) == 74
+    return np.bincount(ii)
+
+
+def _run_passes(plan, steps):
+    """the pass loop of `update_batch` with dummy pyramids -> (pyramids built, kept_rows after every pass)"""
+    res, built, kept = fg._PyramidResidency(plan), 0, []
+    for _ in range(steps):
+        for gi in range(len(plan.groups)):
+            if res.get(gi) is None:
+                vol = object()
+                built += plan.rows[gi]
+                res.offer(gi, vol)
+                assert res.get(gi) in (None, vol)
+        kept.append(res.kept_rows)
+        assert res.kept_rows == sum(n for gi, n in enumerate(plan.rows) if res.get(gi) is not None)
+    return built, kept
+
+
+@pytest.mark.parametrize("args,want", BACKEND_PLANS, ids=[str(a) for a, _ in BACKEND_PLANS])
+def test_backend_chunk_plan_and_pyramid_residency(args, want):
+    (V, gb, chunk_edges, steps), (groups, max_edges, budget_rows, max_rows, policy, n_built) = args, want
+    assert BYTES_PER_PYRAMID == 696320.0
+    cnt = _backend_cnt()
+    plan = fg.plan_backend_chunks(cnt, V, BYTES_PER_PYRAMID, steps, True, gb * 2**30, chunk_edges)
+    assert (plan.groups, plan.max_edges, plan.budget_rows, plan.max_rows) == (groups, max_edges, budget_rows, max_rows)
+    assert (plan.keep_all, plan.keep_some) == (policy == "all", policy == "some")
+    size = {g0: int(cnt[g0:g0 + 8].sum()) for g0 in range(0, len(cnt), 8)}
+    assert [g0 for c in plan.groups for g0 in c] == [g0 for g0 in sorted(size) if size[g0] > 0]
+    assert plan.rows == [sum(size[g0] for g0 in c) * V for c in plan.groups] and plan.max_rows == max(plan.rows)
+    assert all(n <= plan.max_edges * V or len(c) == 1 for c, n in zip(plan.groups, plan.rows))
+    built, kept = _run_passes(plan, steps)
+    assert built == n_built
+    if policy == "all":
+        assert kept == [74 * V] * steps
+    elif policy == "none":
+        assert kept == [0] * steps
+    elif plan.max_rows > plan.budget_rows:
+        # a single group of eight that alone exceeds the budget (the 0.01 GB rows, and two views at 0.04 GB) is still
+        # worked on, and nothing stays resident next to it
+        assert (gb, V) in ((0.01, 1), (0.04, 2), (0.01, 2)) and kept == [0] * steps
+    else:  # what is kept leaves room for the largest chunk
+        assert all(k + plan.max_rows <= plan.budget_rows for k in kept), kept
+    assert kept == kept[:1] * steps and built == 74 * V * steps - kept[0] * (steps - 1)  # later passes rebuild what is not kept
+
+
+def test_backend_chunk_plan_without_volumes_and_without_edges():
+    cnt = _backend_cnt()
+    plan = fg.plan_backend_chunks(cnt, 1, BYTES_PER_PYRAMID, 2, False, 0.04 * 2**30, 1)  # AltCorrBlock: nothing to keep
+    assert (plan.keep_all, plan.keep_some) == (False, False)
+    assert (plan.groups, plan.max_edges, plan.budget_rows, plan.rows) == ([[0], [8], [16]], 8, 61, [29, 32, 13])
+    res = fg._PyramidResidency(plan)
+    for gi in range(3):
+        res.offer(gi, object())
+    assert res.kept_rows == 0 and all(res.get(gi) is None for gi in range(3))
+    empty = fg.plan_backend_chunks(np.zeros(0, dtype=np.int64), 1, BYTES_PER_PYRAMID, 2, True, 160 * 2**30, 4096)
+    assert (empty.groups, empty.rows, empty.max_rows, empty.keep_all, empty.keep_some) == ([], [], 0, True, False)
+    assert _run_passes(empty, 2) == (0, [0, 0])
+
+
 def test_host_csr_groups_the_rows_by_source_node():
     rng = np.random.default_rng(3)
     dix = rng.integers(0, 7, 50)

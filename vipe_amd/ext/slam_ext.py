@@ -106,6 +106,29 @@ PROFILE_EVENTS = None  # measurement aid (bench.py): (event, event[, iteration])
 PLAN_REUSE = True  # False: rebuild the edge plan on every call and launch every kernel of both paths (validation aid)
 
 
+def _ba_problem_params(floats, index, t0, t1, n_iters, pose_damping, pose_ep, camera, alpha, n_poses, *, motion_only,
+                       limited_disp, optimize_intrinsics, optimize_rig_rotation, solver_options):
+    """The argument checks and `vipe_ba_params` that `dense_ba` and `dense_ba_linearize` share; floats = (poses, disps,
+    disps_sens, intrinsics, rig, target, weight, disp_damping), index = (pi, qi, pj, qj, di) -> (p, V, n_poses, ht, wd, M)"""
+    poses, disps, _, _, rig, target, weight, _ = floats
+    _check_camera_options(camera, optimize_intrinsics)
+    check_gpu_contig(*floats, *index)
+    for t in floats:
+        require(t.dtype == torch.float32, "dense_ba / dense_ba_marginals work in float32 (the reference's BA dtype)")
+    V = rig.shape[0]
+    n_poses = poses.shape[0] if n_poses is None else int(n_poses)
+    require(disps.dim() == 3 and disps.shape[0] >= n_poses * V, "disps must be [n_poses*V,ht,wd]")
+    _, ht, wd = disps.shape
+    M = index[0].shape[0]
+    require(target.numel() == M * ht * wd * 2 and weight.numel() == M * ht * wd * 2, "target/weight must be [M,P,2]")
+    p = BAParams(n_poses=n_poses, n_views=V, ht=ht, wd=wd, M=M, t0=int(t0), t1=int(t1), n_iters=int(n_iters),
+                 pose_damping=float(pose_damping), pose_ep=float(pose_ep), motion_only=int(motion_only),
+                 limited_disp=int(limited_disp), optimize_intrinsics=int(optimize_intrinsics),
+                 optimize_rig_rotation=int(optimize_rig_rotation), camera=CAMERA_CODE[camera], alpha=float(alpha),
+                 weight_scale=0.001, intr_factor=8.0, reuse_plan=0, path_hint=0, solver_options=int(solver_options))
+    return p, V, n_poses, ht, wd, M
+
+
 def dense_ba(poses, disps, disps_sens, intrinsics, rig, target, weight, disp_damping, pi, qi, pj, qj, di, t0, t1,
              n_iters, pose_damping, pose_ep, motion_only=False, limited_disp=False, optimize_intrinsics=False,
              optimize_rig_rotation=False, camera="pinhole", alpha=0.001, n_poses=None, want_info=False, state=None,
@@ -121,21 +144,10 @@ def dense_ba(poses, disps, disps_sens, intrinsics, rig, target, weight, disp_dam
     poses [>=n_poses,7]; disps, disps_sens, disp_damping [>=n_poses*V,ht,wd] (flattened views);
     target, weight [M,ht*wd,2]; pi..di [M] int64.  `n_poses` bounds the pose/frame indices that occur
     (default: all rows of `poses`); a tight bound keeps the reduced system small."""
-    _check_camera_options(camera, optimize_intrinsics)
-    check_gpu_contig(poses, disps, disps_sens, intrinsics, rig, target, weight, disp_damping, pi, qi, pj, qj, di)
-    for t in (poses, disps, disps_sens, intrinsics, rig, target, weight, disp_damping):
-        require(t.dtype == torch.float32, "dense_ba works in float32 (the reference's BA dtype)")
-    V = rig.shape[0]
-    n_poses = poses.shape[0] if n_poses is None else int(n_poses)
-    require(disps.dim() == 3 and disps.shape[0] >= n_poses * V, "disps must be [n_poses*V,ht,wd]")
-    _, ht, wd = disps.shape
-    M = pi.shape[0]
-    require(target.numel() == M * ht * wd * 2 and weight.numel() == M * ht * wd * 2, "target/weight must be [M,P,2]")
-    p = BAParams(n_poses=n_poses, n_views=V, ht=ht, wd=wd, M=M, t0=int(t0), t1=int(t1), n_iters=int(n_iters),
-                 pose_damping=float(pose_damping), pose_ep=float(pose_ep), motion_only=int(motion_only),
-                 limited_disp=int(limited_disp), optimize_intrinsics=int(optimize_intrinsics),
-                 optimize_rig_rotation=int(optimize_rig_rotation), camera=CAMERA_CODE[camera], alpha=float(alpha),
-                 weight_scale=0.001, intr_factor=8.0, reuse_plan=0, path_hint=0, solver_options=int(solver_options))
+    floats, index = (poses, disps, disps_sens, intrinsics, rig, target, weight, disp_damping), (pi, qi, pj, qj, di)
+    p, _, _, _, _, M = _ba_problem_params(floats, index, t0, t1, n_iters, pose_damping, pose_ep, camera, alpha, n_poses,
+                                          motion_only=motion_only, limited_disp=limited_disp, solver_options=solver_options,
+                                          optimize_intrinsics=optimize_intrinsics, optimize_rig_rotation=optimize_rig_rotation)
     if overlap is not None:
         p.overlap_stream, p.overlap_fn, p.overlap_user = overlap
     if profile_events is None:
@@ -146,14 +158,12 @@ def dense_ba(poses, disps, disps_sens, intrinsics, rig, target, weight, disp_dam
     L = lib()
     nbytes = L.vipe_dense_ba_workspace_bytes(ctypes.byref(p))
     require(nbytes > 0, "bad BA parameters")
-    ws, key = _plan_workspace(p, nbytes, state, plan_key, camera, (pi, qi, pj, qj, di), poses.device,
-                              launches=M > 0 and int(n_iters) > 0)
+    ws, key = _plan_workspace(p, nbytes, state, plan_key, camera, index, poses.device, launches=M > 0 and int(n_iters) > 0)
     learn = state is not None and key is not None and p.path_hint == 0 and "pending" not in state and M > 0 and n_iters > 0 \
         and not torch.cuda.is_current_stream_capturing() and PLAN_REUSE
     info = torch.zeros(8, dtype=torch.int32, device=poses.device) if (want_info or learn) else None
-    check(L.vipe_dense_ba(ctypes.byref(p), ptr(poses), ptr(disps), ptr(disps_sens), ptr(intrinsics), ptr(rig),
-                          ptr(target), ptr(weight), ptr(disp_damping), ptr(_i64(pi)), ptr(_i64(qi)), ptr(_i64(pj)),
-                          ptr(_i64(qj)), ptr(_i64(di)), ptr(ws), ws.numel(), ptr(info), stream_ptr(poses)), "dense_ba")
+    check(L.vipe_dense_ba(ctypes.byref(p), *map(ptr, floats), *(ptr(_i64(x)) for x in index), ptr(ws), ws.numel(), ptr(info),
+                          stream_ptr(poses)), "dense_ba")
     if learn:  # read the plan's facts back WITHOUT blocking: pinned buffer + event, consulted by a later call
         host = torch.empty(8, dtype=torch.int32, pin_memory=True)
         host.copy_(info, non_blocking=True)
@@ -192,33 +202,20 @@ def dense_ba_linearize(poses, disps, disps_sens, intrinsics, rig, target, weight
     at the given state, which is only read.  -> (S, info, ctx): the damped symmetric reduced system [n,n] float64
     (n = info[3]; reading it back synchronises the stream once), the plan's facts, and what `dense_ba_marginals_apply`
     needs.  Nothing else may run in the workspace between the two halves."""
-    _check_camera_options(camera, optimize_intrinsics)
-    check_gpu_contig(poses, disps, disps_sens, intrinsics, rig, target, weight, disp_damping, pi, qi, pj, qj, di)
-    for t in (poses, disps, disps_sens, intrinsics, rig, target, weight, disp_damping):
-        require(t.dtype == torch.float32, "dense_ba_marginals works in float32 (the reference's BA dtype)")
-    V = rig.shape[0]
-    n_poses = poses.shape[0] if n_poses is None else int(n_poses)
-    require(disps.dim() == 3 and disps.shape[0] >= n_poses * V, "disps must be [n_poses*V,ht,wd]")
-    _, ht, wd = disps.shape
-    M = pi.shape[0]
-    require(target.numel() == M * ht * wd * 2 and weight.numel() == M * ht * wd * 2, "target/weight must be [M,P,2]")
-    p = BAParams(n_poses=n_poses, n_views=V, ht=ht, wd=wd, M=M, t0=int(t0), t1=int(t1), n_iters=1,
-                 pose_damping=float(pose_damping), pose_ep=float(pose_ep), motion_only=int(motion_only),
-                 limited_disp=int(limited_disp), optimize_intrinsics=int(optimize_intrinsics),
-                 optimize_rig_rotation=int(optimize_rig_rotation), camera=CAMERA_CODE[camera], alpha=float(alpha),
-                 weight_scale=0.001, intr_factor=8.0, reuse_plan=0, path_hint=0, solver_options=int(solver_options))
+    floats, index = (poses, disps, disps_sens, intrinsics, rig, target, weight, disp_damping), (pi, qi, pj, qj, di)
+    p, V, n_poses, ht, wd, M = _ba_problem_params(
+        floats, index, t0, t1, 1, pose_damping, pose_ep, camera, alpha, n_poses, motion_only=motion_only, limited_disp=limited_disp,
+        solver_options=solver_options, optimize_intrinsics=optimize_intrinsics, optimize_rig_rotation=optimize_rig_rotation)
     L = lib()
     nbytes = L.vipe_dense_ba_workspace_bytes(ctypes.byref(p))
     check(min(nbytes, 0), "dense_ba_linearize")
-    ws, _ = _plan_workspace(p, nbytes, state, plan_key, camera, (pi, qi, pj, qj, di), poses.device, launches=M > 0)
+    ws, _ = _plan_workspace(p, nbytes, state, plan_key, camera, index, poses.device, launches=M > 0)
     D = intrinsics.shape[1] - 4
     nmax = 6 * n_poses + (V * (1 + D) + 6 * (V - 1) if V > 1 else 1 + D)  # the bound the workspace sizes S by
     S = torch.empty((nmax, nmax), dtype=torch.float64, device=poses.device)
     info = torch.zeros(8, dtype=torch.int32, device=poses.device)
-    check(L.vipe_dense_ba_linearize(ctypes.byref(p), ptr(poses), ptr(disps), ptr(disps_sens), ptr(intrinsics), ptr(rig),
-                                    ptr(target), ptr(weight), ptr(disp_damping), ptr(_i64(pi)), ptr(_i64(qi)),
-                                    ptr(_i64(pj)), ptr(_i64(qj)), ptr(_i64(di)), ptr(ws), ws.numel(), ptr(S), nmax,
-                                    ptr(info), stream_ptr(poses)), "dense_ba_linearize")
+    check(L.vipe_dense_ba_linearize(ctypes.byref(p), *map(ptr, floats), *(ptr(_i64(x)) for x in index), ptr(ws), ws.numel(),
+                                    ptr(S), nmax, ptr(info), stream_ptr(poses)), "dense_ba_linearize")
     n = int(info[3].item())
     return S[:n, :n], info, (p, ws, (n_poses, V, ht, wd))
 

@@ -7,6 +7,7 @@ scatter_mean's index.max(), every _tmult_mat_elements and the CPU spsolve).
 """
 
 import ctypes
+import dataclasses
 import os
 
 import numpy as np
@@ -20,6 +21,7 @@ from .networks import AltCorrBlock, CorrBlock, CorrPool
 # host-side work counters (edge counts known without touching the device): edges x operator applications, correlation
 # pyramids built - what bench.py prices a whole clip's algorithmic bytes / FLOPs with (SURVEY 8d per-edge figures)
 WORK = {"edge_updates": 0, "pyramids_built": 0}
+BACKEND_VOLUME_GB = 160  # default of VIPE_AMD_BACKEND_VOLUME_GB: correlation pyramids `update_batch` keeps, of 288 GB
 
 
 def warm_volume_pool(device, gigabytes=None):
@@ -30,7 +32,7 @@ def warm_volume_pool(device, gigabytes=None):
     clip after clip is warm after its first clip; a benchmark's untimed warm-up should leave the process in that state."""
     if torch.device(device).type != "cuda":
         return 0
-    want = float(gigabytes if gigabytes is not None else os.environ.get("VIPE_AMD_BACKEND_VOLUME_GB", "160")) * 2**30
+    want = float(gigabytes if gigabytes is not None else os.environ.get("VIPE_AMD_BACKEND_VOLUME_GB", BACKEND_VOLUME_GB)) * 2**30
     free, _ = torch.cuda.mem_get_info(device)
     n = int(min(want, 0.85 * free))
     if n <= 0:
@@ -78,6 +80,45 @@ def chunk_groups(cnt, max_edges):
         groups[-1].append(g0)
         size += n8
     return groups
+
+
+BackendChunkPlan = dataclasses.make_dataclass("BackendChunkPlan", frozen=True, fields=[
+    ("groups", list), ("rows", list), ("max_rows", int), ("max_edges", int), ("budget_rows", int), ("keep_all", bool), ("keep_some", bool)])
+# what `FactorGraph._backend_chunk` prepares once per chunk
+_BackendChunk = dataclasses.make_dataclass("_BackendChunk", ["idx_x", "edges", "du", "dixs", "csr", "mask", "xb", "pgate"])
+
+
+def plan_backend_chunks(cnt, n_views, bytes_per_pyramid, steps, use_volume, budget_bytes, chunk_edges):
+    """`update_batch`'s chunks, cnt[f] = edges with source frame f.  With 288 GB of HBM the reference's groups of 8 source
+    keyframes are merged until a chunk holds `chunk_edges` edges (4096: ~110 GB of pyramids at 48 x 64, normally one chunk)
+    or fills the budget, whatever the grid: a pyramid takes 33 MB at 48 x 64, 238 MB at 64 x 128.  -> groups (`chunk_groups`
+    up to max_edges), rows (per chunk its correlation pyramids, one per edge and view; max_rows: the largest chunk's),
+    budget_rows (pyramids the budget holds), keep_all (every chunk's pyramids stay resident over the passes: the feature maps
+    do not change), keep_some (they do not fit - ~4800 edges at 48 x 64, 300+ keyframes: `_PyramidResidency` keeps as MANY as fit)"""
+    keep_all = bool(use_volume and steps > 1 and int(cnt.sum()) * n_views * bytes_per_pyramid <= budget_bytes)
+    keep_some = bool(use_volume and steps > 1 and not keep_all)
+    budget_rows = int(budget_bytes / bytes_per_pyramid)
+    max_edges = max(8, min(chunk_edges, budget_rows // n_views))
+    if keep_some:  # finer chunks: one eighth of the budget each, so that seven of eight budget shares can stay resident
+        max_edges = max(8, min(max_edges, max(256, budget_rows // (8 * n_views))))
+    groups = chunk_groups(cnt, max_edges)
+    rows = [int(sum(cnt[g0:g0 + 8].sum() for g0 in grp)) * n_views for grp in groups]
+    return BackendChunkPlan(groups, rows, max(rows, default=0), max_edges, budget_rows, keep_all, keep_some)
+
+
+class _PyramidResidency:
+    """The pyramids (opaque here) kept over the passes of one `update_batch`, `get(chunk)`: every chunk's, or those offered
+    while they and the largest chunk still fit the budget together; the others are rebuilt every pass (8.5 us per edge)."""
+
+    def __init__(self, plan):
+        self.plan, self._vols, self.kept_rows = plan, {}, 0
+        self.get = self._vols.get
+
+    def offer(self, gi, vol):
+        p, n = self.plan, self.plan.rows[gi]
+        if p.keep_all or (p.keep_some and self.kept_rows + n + p.max_rows <= p.budget_rows):
+            self._vols[gi] = vol
+            self.kept_rows += n
 
 
 def rows_gather(jobs):
@@ -329,8 +370,7 @@ class FactorGraph:
         nk, nd = int(keep_x_np.shape[0]), int(drop_x_np.shape[0])
         if self.corr is not None:
             self.corr = self.corr[keep_x_np]  # host-side index: the pool only edits its slot vector
-        if not self.target.is_contiguous() or not self.weight.is_contiguous():
-            self.target, self.weight = self.target.contiguous(), self.weight.contiguous()
+        self._contiguous_targets()
         row = int(self.target.shape[2] * self.target.shape[3] * 2 * 4)  # one edge's [h, w, 2] f32
         new_t = torch.empty((1, nk) + tuple(self.target.shape[2:]), dtype=self.target.dtype, device=self.device)
         new_w = torch.empty_like(new_t)
@@ -494,7 +534,7 @@ class FactorGraph:
                 n_src = int(du_h.shape[0])
                 csr = tuple(upload_many(host_csr(dix_h, n_src), self.device, torch.int32))
             self._plan = dict(pi=pi, qi=qi, di=di, pj=pj, qj=qj, du=du, dix=dix, n_src=n_src, csr=csr,
-                              t0=int(max(1, ii_h.min() + 1)), t1=int(max(ii_h.max(), jj_h.max()) + 1))
+                              t0=int(max(1, ii_h.min() + 1)), t1=int(max(ii_h.max(), jj_h.max()) + 1), base=int(min(ii_h.min(), jj_h.min())))
         return self._plan
 
     def _inactive_room(self, k):
@@ -546,6 +586,19 @@ class FactorGraph:
         V = self.buffer.n_views
         return (pi - base, qi, di - base * V, pj - base, qj, base)
 
+    def _ba_plan(self, P):  # cached expand_edge_multiview of the edge set, relative to the oldest keyframe used
+        if "ba_plan" not in P:
+            P["ba_plan"] = self._shift_plan((P["pi"], P["qi"], P["di"], P["pj"], P["qj"]), P["base"])
+        return P["ba_plan"]
+
+    @staticmethod
+    def _ba_flags(t0, t1, **flags):  # window, damping and flags of one BA (`bundle_adjustment`): `update`'s, with `flags` over them
+        return dict(dict(t0=t0, t1=t1, pose_damping=1e-3, pose_ep=0.1, motion_only=False, limited_disp=False,
+                         optimize_intrinsics=False, optimize_rig_rotation=False), **flags)
+
+    def _contiguous_targets(self):  # they reach the kernels as addresses of dense [1,E,h,w,2] rows (no-op on such tensors)
+        self.weight, self.target = self.weight.contiguous(), self.target.contiguous()
+
     @torch.no_grad()
     def update(self, t0=None, t1=None, itrs=3, use_inactive=False, motion_only=False, fixed_motion=False,
                limited_disp=False):
@@ -562,8 +615,7 @@ class FactorGraph:
             P["io"] = (torch.empty((E_act, self.ht, self.wd, 2), dtype=torch.float32, device=self.device),
                        torch.empty((E_act, self.ht, self.wd, 4), dtype=torch.float16, device=self.device))
             P["mask"] = buf.masks[P["pi"], P["qi"]].contiguous()
-        if not self.weight.is_contiguous() or not self.target.is_contiguous():
-            self.weight, self.target = self.weight.contiguous(), self.target.contiguous()
+        self._contiguous_targets()
         # motion features + coords1 in one launch (factor_graph.py:253-261)
         coords1, motn = slam_ext.reproject_motion_nhwc(buf.poses, buf.flattened_disps, buf.intrinsics, buf.rig,
                                                        P["pi"], P["qi"], P["pj"], P["qj"], P["di"],
@@ -642,21 +694,14 @@ class FactorGraph:
             target, weight = comb
         else:
             ii, jj, target, weight = self.ii, self.jj, self.target, self.weight
-            if "ba_plan" not in P:  # cached expand_edge_multiview of the edge set, relative to the oldest keyframe used
-                P["ba_plan"] = self._shift_plan((P["pi"], P["qi"], P["di"], P["pj"], P["qj"]),
-                                                int(min(self._index.host["ii"].min(), self._index.host["jj"].min())))
-            plan = P["ba_plan"]
+            plan = self._ba_plan(P)
             plan_key = (self._plan_serial, "act")
         E = target.shape[1]
-        self._last_ba = dict(t0=t0, t1=t1 if not fixed_motion else t0, pose_damping=1e-3, pose_ep=0.1, motion_only=motion_only,
-                             limited_disp=limited_disp, optimize_intrinsics=False, optimize_rig_rotation=False)
+        self._last_ba = self._ba_flags(t0, t1 if not fixed_motion else t0, motion_only=motion_only, limited_disp=limited_disp)
         buf.bundle_adjustment(target.view(E, -1, 2), weight.view(E, -1, 2), self.damping, ii, jj, n_iters=itrs,
                               **self._last_ba, plan=plan, ba_state=self._ba_state, plan_key=plan_key, overlap=ba_overlap)
         if self.upsample:  # after the BA: this iteration's mask on the disparities it has just produced
-            if self.upsample_from_row is None:
-                self._upsample_disps(upmask, P["du"])
-            else:
-                self._upsample_disps(upmask, P["du"], own=self._own_rows(P))
+            self._upsample_disps(upmask, P["du"], own=None if self.upsample_from_row is None else self._own_rows(P))
         if overlap:
             main.wait_stream(self._side)
             self._gate_state = gate_state
@@ -670,20 +715,35 @@ class FactorGraph:
         that `update` / `update_batch` issued (before any: `update`'s own defaults); `t0` / `t1` / `flags` override them.
         Runs in the shared BA workspace, not in this graph's private one."""
         P = self._edge_plan() if int(self.ii.shape[0]) else None
-        ba = dict(self._last_ba or dict(t0=P["t0"] if P else 0, t1=P["t1"] if P else 0, pose_damping=1e-3, pose_ep=0.1,
-                                        motion_only=False, limited_disp=False, optimize_intrinsics=False,
-                                        optimize_rig_rotation=False))
+        ba = dict(self._last_ba or self._ba_flags(P["t0"] if P else 0, P["t1"] if P else 0))
         ba.update(flags)
         ba.update({k: v for k, v in (("t0", t0), ("t1", t1)) if v is not None})
-        plan = None
-        if P is not None:
-            if "ba_plan" not in P:
-                P["ba_plan"] = self._shift_plan((P["pi"], P["qi"], P["di"], P["pj"], P["qj"]),
-                                                int(min(self._index.host["ii"].min(), self._index.host["jj"].min())))
-            plan = P["ba_plan"]
         E = self.target.shape[1]
         return self.buffer.ba_marginals(self.target.contiguous().view(E, -1, 2), self.weight.contiguous().view(E, -1, 2),
-                                        self.damping, self.ii, self.jj, **ba, plan=plan)
+                                        self.damping, self.ii, self.jj, **ba, plan=self._ba_plan(P) if P else None)
+
+    def _backend_chunk(self, plan, gi, eng):
+        """What does not change about chunk `gi` during the passes of `update_batch`, prepared once: idx_x - its rows of the per-edge-
+        and-view tensors (None: the whole graph), edges - their `expand_edge_multiview`; du, dixs, csr - buffer rows of the source
+        nodes, source node of every row, its `host_csr`; mask - the source views' frame masks; xb - the operator's input [n,h,w,320]
+        with the context features and, as the frontend has per edge, pgate - their part of the GRU gates (19 % of its FLOPs) or None"""
+        buf, V, ii_np = self.buffer, self.buffer.n_views, self._index.host["ii"]
+        sel = np.flatnonzero(np.isin(ii_np // 8 * 8, plan.groups[gi]))  # from the host arrays: an index vector, not a mask
+        if sel.shape[0] == ii_np.shape[0]:
+            idx_x, iis, jjs = None, self.ii, self.jj
+        else:
+            idx = upload(sel, self.device)
+            idx_x, iis, jjs = per_view(idx, V), self.ii[idx], self.jj[idx]
+        edges = buf.expand_edge_multiview(iis, jjs)
+        pis, qis = edges[:2]
+        du_np, dixs_np = np.unique(per_view(ii_np[sel], V), return_inverse=True)
+        du, dixs = upload_many([du_np, dixs_np], self.device)
+        mask = buf.masks[pis, qis].contiguous()
+        csr = tuple(upload_many(host_csr(dixs_np, du_np.shape[0]), self.device, torch.int32))
+        xb = torch.empty((plan.rows[gi], self.ht, self.wd, 320), dtype=torch.half, device=self.device)
+        xb[..., 0:128] = buf.inps[pis, qis].permute(0, 2, 3, 1)
+        pgate = eng.gate_context(xb) if eng.supports_gate_split(self.ht, self.wd) else None
+        return _BackendChunk(idx_x=idx_x, edges=edges, du=du, dixs=dixs, csr=csr, mask=mask, xb=xb, pgate=pgate)
 
     @torch.no_grad()
     def update_batch(self, itrs, steps, optimize_intrinsics, optimize_rig_rotation, solver_verbose=False):
@@ -691,9 +751,7 @@ class FactorGraph:
         buffer's feature maps), the flow-update operator applied in chunks of 8 source keyframes, then ONE dense BA
         over all edges with `itrs` Gauss-Newton iterations (t0 = 1, t1 = n_frames, pose damping 1e-5 / 1e-2)."""
         assert self.net_n is not None
-        buf = self.buffer
-        t = buf.n_frames
-        eng = self.update_op.engine(self.device)
+        buf, eng = self.buffer, self.update_op.engine(self.device)
         # The reference's backend uses the volume-free AltCorrBlock to fit 24 GB devices (droid_net.py:121-176).  With
         # 288 GB of HBM the per-chunk volume (~33 MB per edge, ~1.5 GB per chunk of 8 source keyframes) is cheap, and
         # building it (one fused kernel, 10 us per edge) + the fused lookup is >10x faster than 49 x 128-channel dot
@@ -703,65 +761,14 @@ class FactorGraph:
         use_volume = (droid_net_ext.fused_build_covers(buf.flattened_fmaps.shape[1], self.ht, self.wd, 4, buf.flattened_fmaps.dtype)
                       and os.environ.get("VIPE_AMD_BACKEND_ALTCORR") is None)
         corr_op = None if use_volume else AltCorrBlock(buf.flattened_fmaps[None])
-        P = self._edge_plan()
-        V = buf.n_views
-        # The feature maps do not change during the `steps` passes: each chunk's correlation pyramid is built in the
-        # first pass and kept for the others while all of them fit VIPE_AMD_BACKEND_VOLUME_GB (default 160 of 288 GB).
+        P, V = self._edge_plan(), buf.n_views
+        ii_np = self._index.host["ii"]
+        assert self._index.host["jj"].max() >= ii_np.max()
         G_, S_, R_ = droid_net_ext.blocked_dims(self.ht, self.wd)[:3]  # the store is padded to G x 64 sources, R x 4 rows, S x 32 columns
-        vol_bytes = self.ii.shape[0] * V * (G_ * 64) * (R_ * 4 * S_ * 32) * 2 * (1 + 1 / 4 + 1 / 16 + 1 / 64)
-        budget = float(os.environ.get("VIPE_AMD_BACKEND_VOLUME_GB", "160")) * 2**30
-        keep_vols = use_volume and steps > 1 and vol_bytes <= budget
-        # ... and when they do not (more than ~4800 edges at 48 x 64: clips of 300+ keyframes), as MANY chunks as fit next
-        # to the one being worked on stay resident; the others are rebuilt every pass (8.5 us per edge)
-        keep_some = use_volume and steps > 1 and not keep_vols
-        # With 288 GB of HBM the reference's groups of 8 source keyframes are merged (`chunk_groups`) until a chunk holds up
-        # to VIPE_AMD_BACKEND_CHUNK_EDGES edges (default 4096, ~110 GB of pyramids at 48 x 64) - normally one chunk.
-        # Edge indices come from the host arrays; chunks are selected with index vectors, not masks.
-        ii_np, jj_np = self._index.host["ii"], self._index.host["jj"]
-        assert jj_np.max() >= ii_np.max()
-        E_all = ii_np.shape[0]
-        # a chunk's pyramids must fit the volume budget (VIPE_AMD_BACKEND_VOLUME_GB) whatever the grid: 33 MB per edge at
-        # 48 x 64, 238 MB at 64 x 128
-        per_edge = vol_bytes / max(1, self.ii.shape[0] * V)
-        budget_rows = int(budget / per_edge)  # pyramids (one per edge and view) the budget holds
-        max_edges = max(8, min(int(os.environ.get("VIPE_AMD_BACKEND_CHUNK_EDGES", "4096")), budget_rows // V))
-        if keep_some:  # finer chunks: one eighth of the budget each, so that seven of eight budget shares can stay resident
-            max_edges = max(8, min(max_edges, max(256, budget_rows // (8 * V))))
-        cnt = np.bincount(ii_np)
-        groups = chunk_groups(cnt, max_edges)
-        max_rows = max(int(sum(cnt[g0:g0 + 8].sum() for g0 in grp)) for grp in groups) * V  # the largest chunk's pyramids
-        # Everything about a chunk that does not change during the `steps` passes is prepared once: index vectors, the
-        # source-node CSR, the frame masks, the context features in the operator's input buffer and - like the
-        # frontend does per edge - the context-feature part of the GRU gates (19 % of the operator's FLOPs per pass)
-        chunks = {}
-
-        def chunk(gi):
-            c = chunks.get(gi)
-            if c is not None:
-                return c
-            sel = np.flatnonzero(np.isin(ii_np // 8 * 8, groups[gi]))
-            c = dict(whole=sel.shape[0] == E_all)
-            if c["whole"]:
-                iis, jjs = self.ii, self.jj
-                c["idx_x"] = None
-            else:
-                idx = upload(sel, self.device)
-                c["idx_x"] = per_view(idx, V)
-                iis, jjs = self.ii[idx], self.jj[idx]
-            pis, qis, dis, pjs, qjs, djs = buf.expand_edge_multiview(iis, jjs)
-            du_np, dixs_np = np.unique(per_view(ii_np[sel], V), return_inverse=True)
-            du_d, dixs_d = upload_many([du_np, dixs_np], self.device)
-            c.update(pis=pis, qis=qis, dis=dis, pjs=pjs, qjs=qjs, djs=djs, n=sel.shape[0] * V, n_src=int(du_np.shape[0]),
-                     du=du_d, dixs=dixs_d, mask=buf.masks[pis, qis].contiguous())
-            c["csr"] = tuple(upload_many(host_csr(dixs_np, c["n_src"]), self.device, torch.int32))
-            xb = torch.empty((c["n"], self.ht, self.wd, 320), dtype=torch.half, device=self.device)
-            xb[..., 0:128] = buf.inps[pis, qis].permute(0, 2, 3, 1)
-            c["xb"] = xb
-            c["pgate"] = eng.gate_context(xb) if eng.supports_gate_split(self.ht, self.wd) else None
-            chunks[gi] = c
-            return c
-
-        vols, kept_rows = {}, 0
+        plan = plan_backend_chunks(np.bincount(ii_np), V, (G_ * 64) * (R_ * 4 * S_ * 32) * 2 * (1 + 1 / 4 + 1 / 16 + 1 / 64), steps,
+                                   use_volume, float(os.environ.get("VIPE_AMD_BACKEND_VOLUME_GB", BACKEND_VOLUME_GB)) * 2**30,
+                                   int(os.environ.get("VIPE_AMD_BACKEND_CHUNK_EDGES", "4096")))
+        chunks, kept = {}, _PyramidResidency(plan)
         for step in range(steps):
             # the last pass's masks are kept per chunk until its BA has run ([n_src,h,w,576] f16 each: 3.5 MB per source
             # keyframe and view at 48 x 64); earlier passes do not ask for them
@@ -770,49 +777,45 @@ class FactorGraph:
             coords1, motn = slam_ext.reproject_motion_nhwc(buf.poses, buf.flattened_disps, buf.intrinsics, buf.rig,
                                                            P["pi"], P["qi"], P["pj"], P["qj"], P["di"],
                                                            self.target[0].contiguous(), camera=buf.camera_type)
-            for gi in range(len(groups)):
-                c = chunk(gi)
-                whole, idx_x, n = c["whole"], c["idx_x"], c["n"]
-                take = (lambda x: x) if whole else (lambda x: x.index_select(0, idx_x))  # noqa: E731
+            for gi in range(len(plan.groups)):
+                if gi not in chunks:
+                    chunks[gi] = self._backend_chunk(plan, gi, eng)
+                c, n = chunks[gi], plan.rows[gi]
+                take = (lambda x: x) if c.idx_x is None else (lambda x: x.index_select(0, c.idx_x))  # noqa: E731
                 c1 = take(coords1)
+                pis, qis, dis, pjs, qjs, djs = c.edges
                 if use_volume:
-                    vol = vols.get(gi)
+                    vol = kept.get(gi)
                     if vol is None:
-                        corr_n = None  # (holds the previous chunk's levels) they go back to the allocator BEFORE this chunk's are taken
-                        vol = CorrBlock.from_buffer(buf.flattened_fmaps, c["pis"] * V + c["qis"], c["pjs"] * V + c["qjs"],
-                                                    frame_range=(0, t * V) if (self.cross_view and V > 1) else
-                                                    (int(min(ii_np.min(), jj_np.min())) * V,
-                                                     (int(max(ii_np.max(), jj_np.max())) + 1) * V))
+                        corr_n = None  # the previous chunk's lookup handle holds its pyramid: back to the allocator BEFORE this build
+                        lo, hi = (0, buf.n_frames) if (self.cross_view and V > 1) else (P["base"], P["t1"])
+                        vol = CorrBlock.from_buffer(buf.flattened_fmaps, pis * V + qis, pjs * V + qjs, frame_range=(lo * V, hi * V))
                         WORK["pyramids_built"] += n
-                        if keep_vols or (keep_some and kept_rows + n + max_rows <= budget_rows):
-                            vols[gi] = vol
-                            kept_rows += n
+                        kept.offer(gi, vol)
                     corr_n = vol.lookup_deferred(c1)
                 else:
-                    corr1 = corr_op(c1[None], c["dis"], c["djs"])  # [1,n,196,h,w] fp32
+                    corr1 = corr_op(c1[None], dis, djs)  # [1,n,196,h,w] fp32
                     corr_n = torch.zeros((n, self.ht, self.wd, 200), dtype=torch.half, device=self.device)
                     corr_n[..., :196] = corr1[0].permute(0, 2, 3, 1)
-                net, dw, eta, upmask = eng.forward_nhwc(take(self.net_n).contiguous(), c["xb"], corr_n,
-                                                        take(motn).contiguous(), ix=c["dixs"], n_src=c["n_src"],
-                                                        csr=c["csr"], pgate=c["pgate"], **up)
+                net, dw, eta, upmask = eng.forward_nhwc(take(self.net_n).contiguous(), c.xb, corr_n, take(motn).contiguous(),
+                                                        ix=c.dixs, n_src=int(c.du.shape[0]), csr=c.csr, pgate=c.pgate, **up)
                 if up:
-                    upmasks.append((upmask, c["du"]))
+                    upmasks.append((upmask, c.du))
                 WORK["edge_updates"] += n
                 self._gate_state = None
-                if whole:
+                if c.idx_x is None:  # the whole graph
                     self.net_n = net if net.data_ptr() != self.net_n.data_ptr() else net.clone()
-                    if not self.weight.is_contiguous() or not self.target.is_contiguous():
-                        self.weight, self.target = self.weight.contiguous(), self.target.contiguous()
-                    slam_ext.update_finish(c1, dw, c["mask"], self.target, self.weight, eta, c["du"], self.damping)
-                else:
-                    weight = dw[..., 2:4].masked_fill(c["mask"].unsqueeze(-1), 0.0)
-                    self.net_n[idx_x] = net
-                    self.target[0, idx_x] = c1 + dw[..., 0:2]
-                    self.weight[0, idx_x] = weight
-                    self.damping[c["du"]] = eta
+                    self._contiguous_targets()
+                    slam_ext.update_finish(c1, dw, c.mask, self.target, self.weight, eta, c.du, self.damping)
+                else:  # the reference's own ops, not `update_finish`: one form for both would change the launches of this branch
+                    weight = dw[..., 2:4].masked_fill(c.mask.unsqueeze(-1), 0.0)
+                    self.net_n[c.idx_x] = net
+                    self.target[0, c.idx_x] = c1 + dw[..., 0:2]
+                    self.weight[0, c.idx_x] = weight
+                    self.damping[c.du] = eta
             E = self.target.shape[1]
-            self._last_ba = dict(t0=1, t1=t, pose_damping=1e-5, pose_ep=1e-2, motion_only=False, limited_disp=False,
-                                 optimize_intrinsics=optimize_intrinsics, optimize_rig_rotation=optimize_rig_rotation)
+            self._last_ba = self._ba_flags(1, buf.n_frames, pose_damping=1e-5, pose_ep=1e-2, optimize_intrinsics=optimize_intrinsics,
+                                           optimize_rig_rotation=optimize_rig_rotation)
             buf.bundle_adjustment(self.target.view(E, -1, 2), self.weight.view(E, -1, 2), self.damping, self.ii, self.jj,
                                   n_iters=itrs, **self._last_ba, verbose=solver_verbose)
             for upmask, du in upmasks:
