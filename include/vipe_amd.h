@@ -655,13 +655,18 @@ int vipe_update_finish(const float* d_coords1, const float* d_dw, const unsigned
  * ------------------------------------------------------------------------------------------- */
 /* [V,3,H,W] fp32 RGB in [0,1] -> [V,H,W,4] fp16 ((x - mean) / std, 4th channel 0) */
 int vipe_enc_prep(const float* d_img, void* d_x4, int V, int H, int W, void* stream);
-/* 7x7 stride-2 pad-3 stem, 3(+1) -> 32 channels: y [B,H/2,W/2,32] = conv + bias (+ReLU if relu) */
+/* 7x7 stride-2 pad-3 stem, 3(+1) -> 32 channels: y [B,(H-1)/2+1,(W-1)/2+1,32] = conv + bias (+ReLU if relu).
+ * d_out_stats != null: the sum and the sum of squares of the fp16-rounded conv + bias are ADDED to it - the value
+ * BEFORE the activation, whatever `relu` says (instance norm comes before the ReLU, droid_net.py:355-357). */
 int vipe_enc_stem(const void* d_x4, const void* d_w, const float* d_bias, void* d_y, float* d_out_stats, int B, int H,
                   int W, int relu, void* stream);
-/* ksize in {1,3} (pad ksize/2), stride in {1,2}, Cin in {32,64,96,128}, Cout % 32 == 0.
+/* ksize in {1,3} (pad ksize/2), stride in {1,2}, Cin in {32,64,96,128}, Cout a positive multiple of 32 (anything else
+ * VIPE_EINVAL, another ksize / stride VIPE_EUNSUPPORTED).
  * d_in_stats != null: the input is relu(instance_norm(x)) formed on load.  d_res != null (NHWC only):
  * y = relu(res + act(conv)).  nchw: y is [B,Cout,Ho,Wo].  tanh_split >= 0: channels < split get tanh, the others
- * ReLU (context net output, droid_net.py:525-527). */
+ * ReLU (context net output, droid_net.py:525-527).
+ * d_out_stats != null: the sum and the sum of squares of the fp16-rounded conv + bias are ADDED to it - the value
+ * BEFORE the activation: before ReLU, tanh and the residual, so `relu` does not change them. */
 int vipe_enc_conv(const void* d_x, const float* d_in_stats, const void* d_w, const float* d_bias, const void* d_res,
                   void* d_y, float* d_out_stats, int B, int H, int W, int Cin, int Cout, int ksize, int stride,
                   int relu, int nchw, int tanh_split, void* stream);

@@ -385,7 +385,7 @@ VIPE_EXPORT int vipe_enc_conv(const void* d_x, const float* d_in_stats, const vo
                               const void* d_res, void* d_y, float* d_out_stats, int B, int H, int W, int Cin, int Cout,
                               int ksize, int stride, int relu, int nchw, int tanh_split, void* stream) {
   VIPE_CHECK_ARG(d_x && d_w && d_bias && d_y && B > 0 && H > 0 && W > 0);
-  VIPE_CHECK_ARG(Cin % 32 == 0 && Cin <= 128 && Cout % CT == 0);
+  VIPE_CHECK_ARG(Cin > 0 && Cin % 32 == 0 && Cin <= 128 && Cout > 0 && Cout % CT == 0);
   VIPE_CHECK_ARG(!(d_res && nchw));
   EncConvArgs a;
   a.x = (const half_t*)d_x; a.in_stats = d_in_stats; a.in_inv_count = 1.0f / ((float)H * (float)W);

@@ -100,13 +100,15 @@ class BasicEncoder(nn.Module):
         st = stream_ptr(x4)
         n, H, W, _ = x4.shape
         inorm = self.norm_fn == "instance"
-        # one zeroed arena for every statistics buffer of this pass: 14 tensors of at most 128 channels
+        # one zeroed arena for every statistics buffer of this pass: 15 tensors of at most 128 channels (the stem, then
+        # conv1 / conv2 of six blocks and the strided shortcut of two: 4 + 5 + 5)
         arena = torch.zeros((16, n, 128, 2), dtype=torch.float32, device=x4.device) if inorm else None
         slot = [0]
 
         def stats(c):
             if not inorm:
                 return None
+            require(slot[0] < arena.shape[0] and c <= arena.shape[2], "the encoder's statistics arena is exhausted")
             s = arena[slot[0]].view(-1)[: n * c * 2]
             slot[0] += 1
             return s
