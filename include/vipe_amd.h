@@ -770,6 +770,55 @@ int vipe_depth_consistency(const float* d_disp, const float* d_poses, const floa
                            int N, int K, int R, int n_views, int H, int W, int h1, int w1, int top, int left, int H0,
                            int W0, float tol, void* stream);
 
+/* Fused clip point cloud (cloud_fuse.hip; an addition, the ABI version stays 4): the confident pixels of the maps
+ * vipe_depth_export writes, back-projected to the world and accumulated into a voxel hash table that the caller keeps on
+ * the device; vipe_cloud_extract turns the table into one point per voxel.  Integer accumulators throughout: the table's
+ * content does not depend on pixel order, on how the maps are split over launches, or on the run.
+ *   d_disp, d_poses, d_rig, d_intrinsics, intr_dim, camera, d_rows, N, R, n_views, (H, W, h1, w1, top, left, H0, W0): as
+ *   for vipe_depth_consistency; a d_rows entry outside [0, R) contributes nothing
+ *   d_conf [N,H0,W0] u8 (vipe_depth_consistency's bytes) or NULL: a pixel is kept only if (conf & 15) >= min_agree
+ *   d_rgb  [N,H0,W0,3] or NULL, rgb_dtype VIPE_U8 / VIPE_F16 / VIPE_F32 (read only with d_rgb); a float c becomes
+ *          (int)(clamp(c, 0, 1) * 255 + 0.5f)
+ *   stride 1..8: only pixels with x % stride == 0 and y % stride == 0 take part
+ *   inv_voxel = 1 / voxel, rounded once by the caller
+ *   d_keys [cap] int64, empty slots hold -1;  d_acc [cap,8] int32 = {count, sum qx, sum qy, sum qz, sum r, sum g, sum b,
+ *          unused}, 32-bit patterns to be read as UNSIGNED, zero where the slot is empty;  cap a power of two <= 2^30
+ *   d_stats [4] int64, added to: points inserted, dropped because the table was full, out of range, dropped because
+ *          their voxel is saturated.  Their sum grows by the number of kept pixels.
+ * Per pixel that takes part: taps and blended disparity d exactly as vipe_depth_export; d <= 0 (or not a number) skips
+ * the pixel.  (u, v) = (ix0 + lx1, iy0 + ly1);  ray = iproj(intrinsics of r's view, u, v);
+ *   (Rm, t) = ((rig[v]^-1 G[p])^-1 as a matrix and a translation;  Xw = (Rm ray + t d) / d  (vipe_iproj's convention)
+ *   per axis s = Xw * inv_voxel, i = floorf(s): unless |i| < 2^20 on all three (a non-finite s fails) the point is out of
+ *   range;  key = (ix + 2^20) | (iy + 2^20) << 21 | (iz + 2^20) << 42;  q = min(255, (int)((s - i) * 256.0f))
+ *   slot: linear probing from ((uint64(key) * 0x9E3779B97F4A7C15) >> 32) & (cap - 1), wrapping at cap, one 64-bit
+ *   compare-and-swap per empty slot met, at most min(cap, 128) slots - then the point is dropped and counted.  No thread
+ *   waits for another.  acc[slot] += {1, qx, qy, qz, r, g, b} unless its count reads >= 2^23 (saturated, counted): a
+ *   count overshoots 2^23 by less than the threads in flight (< 2^19), so no sum (<= 255 * count) passes 2^32.
+ * Keep the table's load below about 0.7: past that the probe limit starts to drop points.
+ * 1 <= n_views <= 8, R % n_views == 0, intr_dim matching the camera, 0 <= min_agree <= 8, inv_voxel positive and finite,
+ * vipe_depth_export's size and grid conditions, for VIPE_CAM_PANORAMA the identity crop, pointers non-null (d_rows,
+ * d_conf, d_rgb excepted) unless N == 0 (then VIPE_OK, no launch); anything else is VIPE_EINVAL.  One output pixel per
+ * thread in 64 x 4 tiles, the map index in grid.z; a workgroup merges its tile in an LDS hash (256 entries) and sends
+ * each distinct voxel to the table once; the four counters are summed per workgroup first. */
+int vipe_cloud_fuse(const float* d_disp, const float* d_poses, const float* d_rig, const float* d_intrinsics, int intr_dim,
+                    int camera, const int64_t* d_rows, const unsigned char* d_conf, int min_agree, const void* d_rgb,
+                    int rgb_dtype, int stride, float inv_voxel, int64_t* d_keys, int* d_acc, int64_t cap, int64_t* d_stats,
+                    int N, int R, int n_views, int H, int W, int h1, int w1, int top, int left, int H0, int W0,
+                    void* stream);
+
+/* The table of vipe_cloud_fuse -> one point per slot with count >= min_count (>= 1), in no particular order:
+ *   xyz[m]   = (i + (sum q / count + 0.5) / 256) * voxel per axis, evaluated in double and rounded once
+ *   rgb[m]   = (sum c + count / 2) / count in integers (d_rgb NULL: no colour is written)
+ *   count[m], key[m]: the slot's count and key
+ * d_num_out [1] int64 receives the number of such slots - the total, also when it exceeds max_out; then only max_out
+ * points are written (which ones is not defined).  max_out = 0 counts only (the outputs may be NULL).
+ *   d_xyz [max_out,3] f32, d_rgb [max_out,3] u8 or NULL, d_count [max_out] int32, d_key [max_out] int64
+ * cap a power of two <= 2^30, voxel positive and finite, min_count >= 1, max_out >= 0, pointers non-null as stated;
+ * anything else is VIPE_EINVAL.  One memset node (d_num_out) and one launch; one atomic per wave. */
+int vipe_cloud_extract(const int64_t* d_keys, const int* d_acc, int64_t cap, float voxel, int min_count, float* d_xyz,
+                       unsigned char* d_rgb, int* d_count, int64_t* d_key, int64_t max_out, int64_t* d_num_out,
+                       void* stream);
+
 /* ---------------------------------------------------------------------------------------------
  * Sparse keypoint tracker: corner detection and pyramidal Lucas-Kanade (klt_track.hip), the producer of the tracks
  * that `SparseTracks` feeds to the motion filter and to the BA's second flow term.  An addition: the reference's only

@@ -121,6 +121,35 @@ def read_depth_artifacts(path):
             yield frame_idx, torch.from_numpy(d.astype(np.float32))
 
 
+def write_ply(path, cloud):
+    """`SLAMOutput.fused_cloud` (an `interface.FusedCloud`) -> a binary little-endian PLY file: per vertex x, y, z as
+    float, red, green, blue as uchar when the cloud carries colour, and the voxel's hit count as the int property
+    `count`.  Host code: the tensors are brought over once.  -> number of vertices written"""
+    xyz = cloud.xyz.detach().cpu().numpy().astype("<f4", copy=False)
+    count = cloud.count.detach().cpu().numpy().astype("<i4", copy=False)
+    rgb = None if cloud.rgb is None else cloud.rgb.detach().cpu().numpy().astype(np.uint8, copy=False)
+    m = xyz.shape[0]
+    assert xyz.shape == (m, 3) and count.shape == (m,) and (rgb is None or rgb.shape == (m, 3))
+    fields = [("x", "<f4"), ("y", "<f4"), ("z", "<f4")]
+    props = ["property float x", "property float y", "property float z"]
+    if rgb is not None:
+        fields += [("red", "u1"), ("green", "u1"), ("blue", "u1")]
+        props += ["property uchar red", "property uchar green", "property uchar blue"]
+    fields.append(("count", "<i4"))
+    props.append("property int count")
+    v = np.empty(m, dtype=np.dtype(fields))  # packed: 16 bytes per vertex, 19 with colour
+    v["x"], v["y"], v["z"], v["count"] = xyz[:, 0], xyz[:, 1], xyz[:, 2], count
+    if rgb is not None:
+        v["red"], v["green"], v["blue"] = rgb[:, 0], rgb[:, 1], rgb[:, 2]
+    header = "\n".join(["ply", "format binary_little_endian 1.0", f"comment fused cloud, voxel {cloud.voxel:.9g}",
+                        f"element vertex {m}"] + props + ["end_header"]) + "\n"
+    os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+    with open(path, "wb") as f:
+        f.write(header.encode("ascii"))
+        f.write(v.tobytes())
+    return m
+
+
 def save_clip_results(out_dir, results, name_of=lambda r: f"clip_{r.clip_id:05d}"):
     """Rank 0 after `clip_shard.gather_results`: one pose + intrinsics artifact per successful clip."""
     written = []

@@ -11,6 +11,9 @@ vipe/streams/base.py:164-254), intrinsics rescaled on the way in and recovered t
                                that crop and resize to the native size, as depth
     depth_consistency(..)      on the same grid (`vipe_depth_consistency`): per pixel of those maps, how many neighbour
                                rows see its point and how many confirm its disparity; `nearest_keyframes` picks the rows
+    cloud_fuse(..)             on the same grid again (`vipe_cloud_fuse`): the pixels that count reaches `min_agree` on,
+                               back-projected to the world and summed into a voxel hash table on the device;
+                               `cloud_extract` (`vipe_cloud_extract`) makes one point per voxel of it
 
 Decoding stays with the caller: frames arrive as tensors.  The nearest-neighbour `instance` channel of `VideoFrame` is
 not read by the SLAM path and is not carried."""
@@ -172,6 +175,107 @@ def depth_consistency(disp, poses, rig, intrinsics, camera, resize_or_params, ro
                                        ptr(nbr), ptr(out), N, int(nbr.shape[1]), R, V, H, W, h1, w1, top, left, H0, W0,
                                        float(tol), stream_ptr(disp)), "vipe_depth_consistency")
     return out
+
+
+def cloud_table(capacity, device):
+    """An empty voxel hash table for `cloud_fuse` -> (keys [cap] int64 of -1, acc [cap,8] int32 of 0, stats [4] int64 of
+    0); `capacity` a power of two."""
+    cap = int(capacity)
+    require(cap > 0 and cap & (cap - 1) == 0 and cap <= 1 << 30, "capacity: a power of two, at most 2^30")
+    return (torch.full((cap,), -1, dtype=torch.int64, device=device), torch.zeros((cap, 8), dtype=torch.int32, device=device),
+            torch.zeros(4, dtype=torch.int64, device=device))
+
+
+def cloud_fuse(disp, poses, rig, intrinsics, camera, resize_or_params, rows, table, voxel, conf=None, min_agree=0, rgb=None,
+               stride=1):
+    """The maps `depth_export` makes of `disp` and `rows`, back-projected to the world and accumulated into the voxel hash
+    `table` = (keys, acc, stats) of `cloud_table`, one `vipe_cloud_fuse` launch: a pixel takes part if x and y are
+    multiples of `stride`, its blended disparity is positive and - with `conf` [N,H0,W0] uint8, `depth_consistency`'s
+    output for the same rows - the low nibble of its byte is at least `min_agree`; it adds 1, its in-voxel offset in
+    1/256 of `voxel` and - with `rgb` [N,H0,W0,3] uint8 / fp16 / fp32 - its colour to the slot of its voxel.  Integer
+    sums: the table's content does not depend on order, chunking or run.  stats += (inserted, dropped because the table
+    was full, out of range, dropped because the voxel is saturated).
+
+    disp, poses, rig, intrinsics, camera, resize_or_params, rows as for `depth_consistency`.  Device tensors only.  The
+    single route from Python to the kernel.  -> table"""
+    from .._lib import CAMERA_CODE
+    if not disp.is_cuda:
+        raise NotImplementedError("cloud_fuse: device tensors only (vipe_cloud_fuse is a HIP kernel)")
+    require(camera in CAMERA_CODE, f"camera: one of {sorted(CAMERA_CODE)}")
+    require(disp.dim() == 3 and disp.dtype == torch.float32 and disp.is_contiguous(), "disp: contiguous [R,H,W] fp32")
+    R, H, W = (int(v) for v in disp.shape)
+    h1, w1, top, left, H0, W0 = export_params(resize_or_params, H, W)
+    require(rig.dim() == 2 and rig.shape[1] == 7, "rig: [V,7]")
+    V = int(rig.shape[0])
+    require(1 <= V <= 8 and R % V == 0, "rig: 1 to 8 views, and disp holds whole slots (R a multiple of V)")
+    idim = 5 if camera == "mei" else 4
+    for t, shape, what in ((poses, (R // V, 7), "poses"), (rig, (V, 7), "rig"), (intrinsics, (V, idim), "intrinsics")):
+        require(t.is_cuda and t.device == disp.device and t.dtype == torch.float32 and t.is_contiguous()
+                and tuple(t.shape) == shape, f"{what}: contiguous fp32 {list(shape)} on disp's device")
+    if rows is not None:
+        require(rows.is_cuda and rows.device == disp.device and rows.dtype == torch.int64 and rows.dim() == 1
+                and rows.is_contiguous(), "rows: contiguous int64 [N] on disp's device")
+    N = R if rows is None else int(rows.shape[0])
+    if conf is not None:
+        require(conf.is_cuda and conf.device == disp.device and conf.dtype == torch.uint8 and conf.is_contiguous()
+                and tuple(conf.shape) == (N, H0, W0), f"conf: contiguous [{N},{H0},{W0}] uint8 on disp's device")
+    require(0 <= int(min_agree) <= 8, "min_agree: 0 to 8")
+    if rgb is not None:
+        require(rgb.is_cuda and rgb.device == disp.device and rgb.dtype in _RGB_CODE and rgb.is_contiguous()
+                and tuple(rgb.shape) == (N, H0, W0, 3), f"rgb: contiguous [{N},{H0},{W0},3] uint8 / fp16 / fp32 on disp's device")
+    require(1 <= int(stride) <= 8, "stride: 1 to 8")
+    inv_voxel = 1.0 / float(voxel) if float(voxel) > 0 else 0.0
+    require(inv_voxel > 0 and math.isfinite(inv_voxel), "voxel must be positive and finite")
+    keys, acc, stats = _check_table(table, disp.device)
+    check(lib().vipe_cloud_fuse(ptr(disp), ptr(poses), ptr(rig), ptr(intrinsics), idim, CAMERA_CODE[camera], ptr(rows),
+                                ptr(conf), int(min_agree), ptr(rgb), _RGB_CODE[rgb.dtype] if rgb is not None else U8,
+                                int(stride), inv_voxel, ptr(keys), ptr(acc), int(keys.shape[0]), ptr(stats), N, R, V, H, W,
+                                h1, w1, top, left, H0, W0, stream_ptr(disp)), "vipe_cloud_fuse")
+    return table
+
+
+def _check_table(table, device=None):
+    require(isinstance(table, (tuple, list)) and len(table) == 3, "table: (keys, acc, stats) of `cloud_table`")
+    keys, acc, stats = table
+    if not keys.is_cuda:
+        raise NotImplementedError("the voxel hash table lives on the device (the kernels are HIP)")
+    cap = int(keys.shape[0]) if keys.dim() == 1 else 0
+    require(cap > 0 and cap & (cap - 1) == 0, "table keys: [cap], cap a power of two")
+    for t, shape, dtype, what in ((keys, (cap,), torch.int64, "keys"), (acc, (cap, 8), torch.int32, "acc"),
+                                  (stats, (4,), torch.int64, "stats")):
+        require(t.is_cuda and t.dtype == dtype and t.is_contiguous() and tuple(t.shape) == shape
+                and t.device == (device or keys.device), f"table {what}: contiguous {dtype} {list(shape)} on the maps' device")
+    return keys, acc, stats
+
+
+def cloud_extract(table, voxel, min_count=1, color=True, max_out=None):
+    """The table `cloud_fuse` filled -> (xyz [M,3] fp32, rgb [M,3] uint8 or None, count [M] int32, key [M] int64, num): one
+    point per voxel with at least `min_count` points - the centroid, the mean colour (`color`), the number of points,
+    the voxel's key - in the table's order, which means nothing (`interface.FusedCloud` sorts by key).  `num` is the
+    number of such voxels.  With `max_out` None the voxels are counted first (a launch that writes nothing, one
+    read-back) and the outputs hold all of them; with a number the outputs have that many rows, of which the first
+    min(num, max_out) are written.  Device tensors only.  The single route from Python to `vipe_cloud_extract`."""
+    keys, acc, _ = _check_table(table)
+    require(float(voxel) > 0 and math.isfinite(float(voxel)), "voxel must be positive and finite")
+    require(int(min_count) >= 1, "min_count: at least 1")
+    require(max_out is None or int(max_out) >= 0, "max_out: None or a size")
+    dev, cap = keys.device, int(keys.shape[0])
+    num = torch.zeros(1, dtype=torch.int64, device=dev)
+
+    def launch(xyz, rgb, count, key, m):
+        check(lib().vipe_cloud_extract(ptr(keys), ptr(acc), cap, float(voxel), int(min_count), ptr(xyz), ptr(rgb), ptr(count),
+                                       ptr(key), m, ptr(num), stream_ptr(keys)), "vipe_cloud_extract")
+
+    if max_out is None:
+        launch(None, None, None, None, 0)
+        max_out = int(num.item())
+    m = int(max_out)
+    xyz = torch.zeros((m, 3), dtype=torch.float32, device=dev)
+    rgb = torch.zeros((m, 3), dtype=torch.uint8, device=dev) if color else None
+    count = torch.zeros(m, dtype=torch.int32, device=dev)
+    key = torch.full((m,), -1, dtype=torch.int64, device=dev)
+    launch(xyz, rgb, count, key, m)
+    return xyz, rgb, count, key, int(num.item())
 
 
 def nearest_keyframes(frame_tstamps, kf_tstamps, kf_valid, k):

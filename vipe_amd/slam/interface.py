@@ -90,6 +90,41 @@ def rescale_frame_depths(frame_depths, s):
     return (frame_depths.float() * s).to(frame_depths.dtype)
 
 
+class FusedCloud:
+    """`SLAMOutput.fused_cloud` (`SLAMConfig.fused_cloud`): one point per occupied voxel of the clip's voxel
+    hash - `xyz` [M,3] fp32 the centroid of the voxel's points (in the trajectory's units, quantised to 1/256 of a
+    voxel per point), `rgb` [M,3] uint8 their mean colour or None when no colour was fed, `count` [M] int32 how many
+    pixels fell in, `key` [M] int64 the voxel's index (ix + 2^20) | (iy + 2^20) << 21 | (iz + 2^20) << 42 - sorted by
+    `key` (the table's own order means nothing), `voxel` the edge length, `stats` a dict of the four counters of
+    `vipe_cloud_fuse`: inserted, dropped_full, out_of_range, saturated."""
+
+    STATS = ("inserted", "dropped_full", "out_of_range", "saturated")
+
+    def __init__(self, xyz, rgb, count, key, voxel, stats):
+        key, order = torch.sort(key)
+        self.xyz, self.count, self.key = xyz[order], count[order], key
+        self.rgb = None if rgb is None else rgb[order]
+        self.voxel = float(voxel)
+        self.stats = dict(zip(self.STATS, (int(v) for v in stats))) if not isinstance(stats, dict) else dict(stats)
+
+    def __len__(self):
+        return int(self.key.shape[0])
+
+    def voxel_index(self):
+        """-> int64 [M,3]: the voxels' integer coordinates, decoded from `key`"""
+        return torch.stack([((self.key >> (21 * i)) & 0x1FFFFF) - (1 << 20) for i in range(3)], dim=1)
+
+
+def rescale_fused_cloud(cloud, s):
+    """`SLAMOutput.fused_cloud` of a result that is rescaled by the metric-depth factor `s` the way `FilledReturn.scale`
+    does it (disparities / s, translations * s): points * s, voxel * s; colours, counts and keys (voxel indices) stay.
+    -> a new `FusedCloud`."""
+    out = FusedCloud.__new__(FusedCloud)
+    out.xyz, out.voxel = cloud.xyz * s, cloud.voxel * float(s)
+    out.rgb, out.count, out.key, out.stats = cloud.rgb, cloud.count, cloud.key, dict(cloud.stats)
+    return out
+
+
 def unpack_depth_conf(conf):
     """`SLAMOutput.frame_depth_conf` (or one map of a `frame_depth_conf_sink`), uint8 -> (agree, visible), two uint8
     tensors of its shape: of the pixel's neighbour keyframes, how many confirm its depth and how many see its point at
@@ -123,13 +158,17 @@ class SLAMOutput:
 
     None unless `SLAMConfig.frame_depth_conf` (and no `frame_depth_conf_sink`): `frame_depth_conf` [T,V,H0,W0] uint8,
     pixel for pixel beside `frame_depths`: the multi-view consistency count against the frame's nearest keyframes of
-    the same view, agree | visible << 4 (`unpack_depth_conf`)."""
+    the same view, agree | visible << 4 (`unpack_depth_conf`).
+
+    None unless `SLAMConfig.fused_cloud`: `fused_cloud`, a `FusedCloud` - the confident pixels of all those maps in one
+    voxel-fused, coloured point cloud of bounded size (`rescale_fused_cloud` for a metric factor,
+    `driver.artifacts.write_ply` for a file)."""
 
     def __init__(self, *, trajectory, intrinsics, rig=None, slam_map=None, ba_residual=0.0, keyframe_disps_up=None,
                  keyframe_disps_up_valid=None, keyframe_disp_var=None, keyframe_pose_cov=None, frame_depths=None,
-                 frame_disps_lowres=None, frame_depth_conf=None):
+                 frame_disps_lowres=None, frame_depth_conf=None, fused_cloud=None):
         self.frame_depths, self.frame_disps_lowres = frame_depths, frame_disps_lowres
-        self.frame_depth_conf = frame_depth_conf
+        self.frame_depth_conf, self.fused_cloud = frame_depth_conf, fused_cloud
         self.keyframe_disp_var, self.keyframe_pose_cov = keyframe_disp_var, keyframe_pose_cov
         self.trajectory, self.intrinsics, self.rig, self.slam_map, self.ba_residual = trajectory, intrinsics, rig, slam_map, ba_residual
         self.keyframe_disps_up, self.keyframe_disps_up_valid = keyframe_disps_up, keyframe_disps_up_valid

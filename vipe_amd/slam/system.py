@@ -74,7 +74,19 @@ class SLAMConfig:
     frame_depth_conf_tol: float = 0.05     # relative disparity (= depth) difference that still agrees; `map_filter_thresh`'s value
     frame_depth_conf_sink: object = None   # callable (frame_idx, view_idx, conf [H0,W0] uint8 device tensor), in frame order;
                                            # `frame_depth_conf` then stays None
-    sparse_tracks: str = None      # "klt": `run` builds a `KLTSparseTracks(n_views)` (corners + pyramidal Lucas-Kanade in
+    fused_cloud: bool = False      # one voxel-fused point cloud per clip (`SLAMOutput.fused_cloud`): one
+                                   # `vipe_cloud_fuse` launch per chunk behind the consistency launch, on its rows and its
+                                   # bytes, into a hash table that stays on the device; one `vipe_cloud_extract` after pass
+                                   # 2.  Needs `frame_depth` and `frame_depth_conf`.  It only reads.  Off: nothing is
+                                   # allocated, no launch differs
+    fused_cloud_voxel: float = 0.02        # voxel edge in the trajectory's units (a default, not a measurement)
+    fused_cloud_min_agree: int = 2         # keyframes that must confirm a pixel's depth (0 to 8; `frame_depth_conf`'s low nibble)
+    fused_cloud_stride: int = 1            # every stride-th pixel in x and y (1 to 8)
+    fused_cloud_capacity: int = 1 << 22    # slots of the table (a power of two; 40 bytes each); a full table drops points
+                                           # and `FusedCloud.stats` says how many
+    fused_cloud_min_count: int = 2         # points a voxel needs to be extracted
+    fused_cloud_color: bool = True         # mean colour per voxel from the frames handed to `run`
+    sparse_tracks: str = None     # "klt": `run` builds a `KLTSparseTracks(n_views)` (corners + pyramidal Lucas-Kanade in
                                    # HIP) when the caller passed no tracker - the motion filter's track score and the BA's
                                    # track term get real tracks.  None: no tracker is built, nothing is launched or changed
     backend_lock_path: str = None        # ... and let their global-BA phases - each fills the chip by itself and wants the
@@ -108,6 +120,16 @@ class SLAMSystem:
             assert c.frame_depth, "SLAMConfig.frame_depth_conf rates the maps of frame_depth: set frame_depth=True as well"
             assert 1 <= int(c.frame_depth_conf_neighbours) <= 8, "SLAMConfig.frame_depth_conf_neighbours: 1 to 8"
             assert c.frame_depth_conf_tol > 0, "SLAMConfig.frame_depth_conf_tol must be positive"
+        if self.config.fused_cloud:
+            c = self.config
+            assert c.frame_depth and c.frame_depth_conf, \
+                "SLAMConfig.fused_cloud fuses the maps of frame_depth that frame_depth_conf rates: set both as well"
+            assert c.fused_cloud_voxel > 0 and c.fused_cloud_voxel < float("inf"), "SLAMConfig.fused_cloud_voxel must be positive and finite"
+            assert 0 <= int(c.fused_cloud_min_agree) <= 8, "SLAMConfig.fused_cloud_min_agree: 0 to 8"
+            assert 1 <= int(c.fused_cloud_stride) <= 8, "SLAMConfig.fused_cloud_stride: 1 to 8"
+            cap = int(c.fused_cloud_capacity)
+            assert 0 < cap <= 1 << 30 and cap & (cap - 1) == 0, "SLAMConfig.fused_cloud_capacity: a power of two, at most 2^30"
+            assert int(c.fused_cloud_min_count) >= 1, "SLAMConfig.fused_cloud_min_count: at least 1"
         self._config_tracker = sparse_tracks is None and self.config.sparse_tracks == "klt"  # then a fresh one per run
         self._resizes = None  # one `StandardResize` per view inside `run(..., native_resolution=True)`, None outside it
         # system.py:91 builds a tracker from the config; here the caller's (`track_image(frames)` per frame of pass 1,
@@ -288,6 +310,10 @@ class SLAMSystem:
             if self.config.frame_depth_conf_sink is None:
                 size = self._resizes[0].native_size if native else (b.height, b.width)
                 self.frame_depth_conf = torch.zeros((total, b.n_views) + tuple(size), dtype=torch.uint8, device=self.device)
+        self._cloud = None
+        if self.config.fused_cloud:  # the clip's voxel hash and the frames whose colours go into it
+            from .ingest import cloud_table
+            self._cloud = (cloud_table(self.config.fused_cloud_capacity, self.device), frames)
         for c0 in range(0, total, chunk):
             idx = range(c0, min(c0 + chunk, total))
             pre = [self._features(frames[i]) for i in idx]
@@ -330,6 +356,8 @@ class SLAMSystem:
         out = depth_export(b.flattened_disps_up, self._resizes[0] if self._resizes is not None else None, rows=rows,
                            out=out, dtype=c.frame_depth_dtype)
         conf = self._depth_confidence(frame_ids, rows) if c.frame_depth_conf else None  # reads the rows the export read
+        if self._cloud is not None:
+            self._fuse_cloud(frame_ids, rows, conf)
         b.disps_up_valid[s:s + n] = False
         if c.frame_depth_sink is not None:
             for j, f in enumerate(frame_ids):
@@ -362,6 +390,34 @@ class SLAMSystem:
         return ingest.depth_consistency(b.flattened_disps_up, b.poses, b.rig, b.intrinsics, b.camera_type,
                                         self._resizes[0] if self._resizes is not None else None, rows,
                                         upload(nbr.view(n * V, K), self.device), c.frame_depth_conf_tol, out=out)
+
+    def _fuse_cloud(self, frame_ids, rows, conf):
+        """`SLAMConfig.fused_cloud` for the chunk `_depth_confidence` has just rated, before its slots are released: ONE
+        `vipe_cloud_fuse` launch over the same `rows`, gated by the bytes just made (whether they are kept or go to a
+        sink), coloured by the chunk's frames as they were handed to `run` (stacked on the device: at the native size
+        with native_resolution, at SLAM resolution otherwise - the grid of the export either way)."""
+        from . import ingest
+        b, c = self.buffer, self.config
+        table, frames = self._cloud
+        rgb = None
+        if c.fused_cloud_color:
+            rgb = torch.stack([fr.rgb.to(self.device) for f in frame_ids for fr in frames[f]])
+            if rgb.dtype not in (torch.uint8, torch.float16, torch.float32):
+                rgb = rgb.float()
+        ingest.cloud_fuse(b.flattened_disps_up, b.poses, b.rig, b.intrinsics, b.camera_type,
+                          self._resizes[0] if self._resizes is not None else None, rows, table, c.fused_cloud_voxel,
+                          conf=conf, min_agree=c.fused_cloud_min_agree, rgb=rgb, stride=c.fused_cloud_stride)
+
+    def _extract_cloud(self):
+        """After pass 2: ONE `cloud_extract` of the clip's table -> `FusedCloud` (one sort by key; the counters' read-back)."""
+        from . import ingest
+        from .interface import FusedCloud
+        c = self.config
+        table, _ = self._cloud
+        self._cloud = None
+        xyz, rgb, count, key, _ = ingest.cloud_extract(table, c.fused_cloud_voxel, min_count=c.fused_cloud_min_count,
+                                                       color=c.fused_cloud_color)
+        return FusedCloud(xyz, rgb, count, key, c.fused_cloud_voxel, table[2].tolist())
 
     def _check_camera(self, camera_type, frames, native_resolution):
         """What a camera model rules out, before anything is built or touches the device.  The panorama
@@ -429,7 +485,13 @@ class SLAMSystem:
         `frame_depths` (or every map goes to `SLAMConfig.frame_depth_conf_sink`): how many of the frame's nearest
         keyframes of the same view see the pixel's point (high nibble) and how many of those confirm its depth within
         `frame_depth_conf_tol` (low nibble; `interface.unpack_depth_conf`).  It only reads: depths and trajectory are
-        what they are without it."""
+        what they are without it.
+
+        With `SLAMConfig.fused_cloud` on top of both, `fused_cloud` is an `interface.FusedCloud`: every pixel of those
+        maps that at least `fused_cloud_min_agree` keyframes confirm, back-projected to the world and merged per voxel of
+        `fused_cloud_voxel` (centroid, mean colour of the frames' `rgb`, count), voxels with fewer than
+        `fused_cloud_min_count` points left out, sorted by voxel key.  The table has `fused_cloud_capacity` slots and does
+        not grow: `fused_cloud.stats` counts what it dropped.  It only reads as well."""
         frames = [f if isinstance(f, (list, tuple)) else [f] for f in frames]
         total, n_views = len(frames), len(frames[0])
         assert total > 0 and all(len(f) == n_views for f in frames)
@@ -486,4 +548,6 @@ class SLAMSystem:
         if self.config.frame_depth_conf:
             up.update(frame_depth_conf=self.frame_depth_conf)
             self.frame_depth_conf = None
+        if self.config.fused_cloud:
+            up.update(fused_cloud=self._extract_cloud())
         return SLAMOutput(trajectory=filled.poses.inv(), intrinsics=intrinsics, rig=SE3(b.rig.clone()), slam_map=slam_map, **up)
