@@ -819,6 +819,62 @@ int vipe_cloud_extract(const int64_t* d_keys, const int* d_acc, int64_t cap, flo
                        unsigned char* d_rgb, int* d_count, int64_t* d_key, int64_t max_out, int64_t* d_num_out,
                        void* stream);
 
+/* The fused cloud seen from cameras again (cloud_render.hip; an addition, the ABI version stays 4): world points are
+ * splatted into a 64-bit z-buffer per target image that the caller keeps on the device; vipe_cloud_resolve turns the
+ * buffer into depth, colour and index images.  Packed integer minima throughout: the buffer's content depends only on the
+ * set of (point, index) pairs drawn - not on point order, on how the cloud is split over launches, on calling twice, or
+ * on the run.
+ *   d_xyz [M,3] f32 world points; point m carries the index index_base + m; index_base >= 0, index_base + M <= 2^31 - 1
+ *   d_cams [B,7] f32 world -> camera of each target image (the caller composes rig[v]^-1 G[f]; the quaternion is
+ *          normalised on load); d_intrinsics [B,intr_dim] at SLAM resolution, one row per image (intr_dim 4 for
+ *          VIPE_CAM_PINHOLE and VIPE_CAM_PANORAMA, whose rows are never read; 5 for VIPE_CAM_MEI)
+ *   (H, W, h1, w1, top, left, H0, W0): the export geometry of vipe_depth_export with its conditions, H0, W0 <= 2^24; the
+ *          images are the native-size grid [H0,W0]
+ *   point_size >= 0, finite: the points' edge length in world units;  max_radius 0..4
+ *   d_zbuf [B,H0,W0] uint64 in int64 storage; an empty pixel holds all ones (-1)
+ *   d_stats [3] int64, added to: pairs drawn (at least one pixel written or tested), pairs invalid, pairs outside the
+ *          image.  Their sum grows by M * B per launch.
+ * Per point m and image b, every product and sum rounded on its own (no contraction):
+ *   Xc = R X + t, per row ((R_i0 X0 + R_i1 X1) + R_i2 X2) + t_i.  Unless all of Xc is finite the pair is OUTSIDE (so is
+ *   every point with a NaN or an infinite coordinate); else unless Xc.z > 0.1 (pinhole, MEI) or, panorama, |Xc| > 0.1
+ *   and |(Xc.x, Xc.z)| > 1e-3 |Xc| (vipe_reproject's `valid`), the pair is INVALID
+ *   z = Xc.z (pinhole, MEI) or sqrtf((X X + Z Z) + Y Y) (panorama: a range, as the panorama's frame depths are)
+ *   (x, y) = the camera's projection in SLAM-grid coordinates, as vipe_depth_consistency projects
+ *   per axis p = floorf(((x + off) + 0.5f) / scale), off = left | top, scale = float(w1) / float(W0) | float(h1) / float(H0):
+ *   the forward form of the mapping whose inverse vipe_depth_export evaluates.  The crop band the export replicate-pads is
+ *   a real part of the camera's image here: points that project into it are drawn there.  Unless
+ *   -max_radius - 1 <= p <= n_out + max_radius on both axes - compared as floats, before anything becomes an integer; a
+ *   NaN fails - the pair is OUTSIDE
+ *   q = (0.5f * point_size) * foc / z, foc = fx / scale_x (pinhole, MEI; rounded once per image) or float(W0) / (2 pi)
+ *   (panorama);  r = q >= max_radius ? max_radius : (int)q
+ *   footprint [px - r, px + r] x [py - r, py + r]; rows clipped to [0, H0), columns clipped to [0, W0) - the panorama's
+ *   columns are taken modulo W0 instead (its rows are clipped).  No pixel left: OUTSIDE
+ *   value = (uint64)float_as_uint(z) << 32 | (uint32)(index_base + m); every footprint pixel takes
+ *   min(zbuf[b][y][x], value) atomically.  z > 0, so its bit pattern orders as the number does; equal depths go to the
+ *   lower index.  No thread waits for another.
+ * camera, intr_dim and the panorama's identity crop as for vipe_depth_consistency; M >= 0, 0 <= B <= 65535; pointers
+ * non-null unless M == 0 or B == 0 (then VIPE_OK, no launch); anything else is VIPE_EINVAL.  One thread per point, 256
+ * per workgroup, the image in grid.y; the image's matrix and intrinsics are built once per workgroup in LDS; the shipped
+ * form loads a pixel and skips the atomic when the stored value is already <= the candidate (values only decrease, so a
+ * stale read costs at most an atomic; the always-atomic form of the same source leaves the same bits); the counters are
+ * summed per workgroup first. */
+int vipe_cloud_render(const float* d_xyz, int64_t M, int index_base, const float* d_cams, const float* d_intrinsics,
+                      int intr_dim, int camera, int B, int H, int W, int h1, int w1, int top, int left, int H0, int W0,
+                      float point_size, int max_radius, int64_t* d_zbuf, int64_t* d_stats, void* stream);
+
+/* The z-buffer of vipe_cloud_render -> images, one thread per pixel, no atomics:
+ *   d_depth [B,H0,W0], depth_dtype VIPE_F32 (the upper word as a float) or VIPE_F16 (its round-to-nearest-even, as
+ *          vipe_depth_export rounds); 0 where the pixel is empty
+ *   d_index [B,H0,W0] int32 or NULL: the lower word, the winner's index; -1 where empty
+ *   d_rgb_out [B,H0,W0,3] u8 or NULL: d_rgb_points[index] with d_rgb_points [M_total,3] u8; 0 where empty.  A winner index
+ *          outside [0, M_total) with colour requested is a caller error: the load is guarded and the pixel's colour is 0
+ *          (never a fault); so it is when d_rgb_points is NULL, which is accepted only with M_total == 0
+ * B >= 0, H0, W0 > 0, M_total >= 0, d_zbuf and d_depth non-null unless B == 0 (then VIPE_OK, no launch); anything else
+ * is VIPE_EINVAL. */
+int vipe_cloud_resolve(const int64_t* d_zbuf, int B, int H0, int W0, void* d_depth, int depth_dtype,
+                       const unsigned char* d_rgb_points, int64_t M_total, unsigned char* d_rgb_out, int* d_index,
+                       void* stream);
+
 /* ---------------------------------------------------------------------------------------------
  * Sparse keypoint tracker: corner detection and pyramidal Lucas-Kanade (klt_track.hip), the producer of the tracks
  * that `SparseTracks` feeds to the motion filter and to the BA's second flow term.  An addition: the reference's only

@@ -76,7 +76,8 @@ class DepthZipWriter:
     `<frame_idx:05d>.exr` - usable as `SLAMConfig.frame_depth_sink`, so that a long clip's native-size maps leave the
     device as pass 2's chunks complete (each call copies its map to the host).  One archive holds one view's maps (the
     reference writes one `depth/<name>.zip` per stream): calls for other views than `view_idx` are ignored.  Close it
-    (or use it as a context manager) before reading the file."""
+    (or use it as a context manager) before reading the file.  `SLAMConfig.fused_depth_sink` has the same contract: a
+    second writer (another archive) takes the fused cloud's maps as it is, after pass 2."""
 
     def __init__(self, path, view_idx=0):
         os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)

@@ -14,6 +14,9 @@ vipe/streams/base.py:164-254), intrinsics rescaled on the way in and recovered t
     cloud_fuse(..)             on the same grid again (`vipe_cloud_fuse`): the pixels that count reaches `min_agree` on,
                                back-projected to the world and summed into a voxel hash table on the device;
                                `cloud_extract` (`vipe_cloud_extract`) makes one point per voxel of it
+    cloud_render(..)           the way back into the cameras (`vipe_cloud_render`): points splatted into a 64-bit
+                               z-buffer (`cloud_zbuffer`) on that grid; `cloud_resolve` (`vipe_cloud_resolve`) makes
+                               depth, colour and index images of it
 
 Decoding stays with the caller: frames arrive as tensors.  The nearest-neighbour `instance` channel of `VideoFrame` is
 not read by the SLAM path and is not carried."""
@@ -276,6 +279,95 @@ def cloud_extract(table, voxel, min_count=1, color=True, max_out=None):
     key = torch.full((m,), -1, dtype=torch.int64, device=dev)
     launch(xyz, rgb, count, key, m)
     return xyz, rgb, count, key, int(num.item())
+
+
+def render_params(resize_or_params, zbuf_size=None):
+    """-> (H, W, h1, w1, top, left, H0, W0) of `vipe_cloud_render`: from a `StandardResize`, from such a tuple as it is,
+    from a size (H, W) - the identity at that size - or, None, the identity at `zbuf_size`"""
+    r = resize_or_params
+    if r is None:
+        require(zbuf_size is not None, "no geometry given")
+        r = zbuf_size
+    if isinstance(r, StandardResize):
+        return (*r.out_size, *r.size, r.crop[0], r.crop[2], *r.native_size)
+    p = tuple(int(v) for v in r)
+    if len(p) == 2:
+        return (*p, *p, 0, 0, *p)
+    require(len(p) == 8, "render geometry: a StandardResize, (H, W) or (H, W, h1, w1, top, left, H0, W0)")
+    return p
+
+
+def cloud_zbuffer(B, H0, W0, device):
+    """An empty z-buffer for `cloud_render` -> [B,H0,W0] int64 of -1 (all ones: as uint64 the largest value)"""
+    B, H0, W0 = int(B), int(H0), int(W0)
+    require(B >= 0 and H0 > 0 and W0 > 0, "z-buffer: B >= 0 images of a positive size")
+    return torch.full((B, H0, W0), -1, dtype=torch.int64, device=device)
+
+
+def cloud_render(xyz, cams, intrinsics, camera, resize_or_params, zbuf, point_size, max_radius=2, index_base=0, stats=None):
+    """World points splatted into the z-buffer `zbuf` of `cloud_zbuffer`, one `vipe_cloud_render` launch: point m is
+    carried into each of the B cameras `cams` (world -> camera rows), projected with that image's `intrinsics` row onto
+    the export grid of `resize_or_params` (`render_params`: a `StandardResize`, (H, W) for the identity, the eight
+    numbers, or None for the identity at the buffer's size), and every pixel of its square footprint - radius
+    min(max_radius, int(0.5 * point_size * focal / depth)) pixels - takes the minimum of what it holds and
+    (depth bits << 32 | index_base + m).  Integer minima: the buffer does not depend on order, chunking or run, and
+    rendering twice changes nothing.  stats [3] int64 += (pairs drawn, invalid, outside the image); a fresh one when None.
+
+    xyz [M,3] fp32; cams [B,7] fp32; intrinsics [B,4] ([B,5] MEI) at SLAM resolution; camera "pinhole" / "mei" /
+    "panorama" (identity crop only); zbuf [B,H0,W0] int64.  Device tensors only.  The single route from Python to the
+    kernel.  -> stats"""
+    from .._lib import CAMERA_CODE
+    if not (xyz.is_cuda and zbuf.is_cuda):
+        raise NotImplementedError("cloud_render: device tensors only (vipe_cloud_render is a HIP kernel)")
+    require(camera in CAMERA_CODE, f"camera: one of {sorted(CAMERA_CODE)}")
+    require(xyz.dim() == 2 and xyz.shape[1] == 3 and xyz.dtype == torch.float32 and xyz.is_contiguous(), "xyz: contiguous [M,3] fp32")
+    require(zbuf.dim() == 3 and zbuf.dtype == torch.int64 and zbuf.is_contiguous() and zbuf.device == xyz.device,
+            "zbuf: contiguous [B,H0,W0] int64 on the points' device (`cloud_zbuffer`)")
+    M, (B, H0, W0) = int(xyz.shape[0]), (int(v) for v in zbuf.shape)
+    H, W, h1, w1, top, left, h0, w0 = render_params(resize_or_params, (H0, W0))
+    require((h0, w0) == (H0, W0), f"the z-buffer's images are {H0} x {W0}, the geometry's {h0} x {w0}")
+    idim = 5 if camera == "mei" else 4
+    for t, shape, what in ((cams, (B, 7), "cams"), (intrinsics, (B, idim), "intrinsics")):
+        require(t.is_cuda and t.device == xyz.device and t.dtype == torch.float32 and t.is_contiguous()
+                and tuple(t.shape) == shape, f"{what}: contiguous fp32 {list(shape)} on the points' device")
+    require(float(point_size) >= 0 and math.isfinite(float(point_size)), "point_size: a finite length, not negative")
+    require(0 <= int(max_radius) <= 4, "max_radius: 0 to 4")
+    require(int(index_base) >= 0 and int(index_base) + M <= 2 ** 31 - 1, "index_base + M must stay below 2^31")
+    if stats is None:
+        stats = torch.zeros(3, dtype=torch.int64, device=xyz.device)
+    require(stats.is_cuda and stats.device == xyz.device and stats.dtype == torch.int64 and stats.is_contiguous()
+            and tuple(stats.shape) == (3,), "stats: contiguous int64 [3] on the points' device")
+    check(lib().vipe_cloud_render(ptr(xyz), M, int(index_base), ptr(cams), ptr(intrinsics), idim, CAMERA_CODE[camera], B, H, W,
+                                  h1, w1, top, left, H0, W0, float(point_size), int(max_radius), ptr(zbuf), ptr(stats),
+                                  stream_ptr(xyz)), "vipe_cloud_render")
+    return stats
+
+
+def cloud_resolve(zbuf, rgb_points=None, dtype=torch.float16, want_index=False):
+    """The z-buffer `cloud_render` filled -> (depth [B,H0,W0] of `dtype`, rgb [B,H0,W0,3] uint8 or None, index [B,H0,W0]
+    int32 or None), one `vipe_cloud_resolve` launch: the winner's depth (0 where nothing was drawn; fp16 is the
+    round-to-nearest-even of the fp32 value), with `rgb_points` [M,3] uint8 its colour (0 where nothing was drawn, and
+    for an index past M), with `want_index` its index (-1 where nothing was drawn).  Device tensors only.  The single
+    route from Python to the kernel."""
+    if not zbuf.is_cuda:
+        raise NotImplementedError("cloud_resolve: device tensors only (vipe_cloud_resolve is a HIP kernel)")
+    require(zbuf.dim() == 3 and zbuf.dtype == torch.int64 and zbuf.is_contiguous(), "zbuf: contiguous [B,H0,W0] int64")
+    require(dtype in (torch.float16, torch.float32), "dtype: float16 or float32")
+    B, H0, W0 = (int(v) for v in zbuf.shape)
+    require(H0 > 0 and W0 > 0, "zbuf: images of a positive size")
+    M = 0
+    if rgb_points is not None:
+        require(rgb_points.is_cuda and rgb_points.device == zbuf.device and rgb_points.dtype == torch.uint8
+                and rgb_points.dim() == 2 and rgb_points.shape[1] == 3 and rgb_points.is_contiguous(),
+                "rgb_points: contiguous [M,3] uint8 on the buffer's device")
+        M = int(rgb_points.shape[0])
+    depth = torch.empty((B, H0, W0), dtype=dtype, device=zbuf.device)
+    rgb = torch.empty((B, H0, W0, 3), dtype=torch.uint8, device=zbuf.device) if rgb_points is not None else None
+    index = torch.empty((B, H0, W0), dtype=torch.int32, device=zbuf.device) if want_index else None
+    check(lib().vipe_cloud_resolve(ptr(zbuf), B, H0, W0, ptr(depth), F16 if dtype == torch.float16 else F32,
+                                   ptr(rgb_points) if M else None, M, ptr(rgb), ptr(index), stream_ptr(zbuf)),
+          "vipe_cloud_resolve")
+    return depth, rgb, index
 
 
 def nearest_keyframes(frame_tstamps, kf_tstamps, kf_valid, k):

@@ -86,7 +86,8 @@ def rescale_frame_depths(frame_depths, s):
     """`SLAMOutput.frame_depths` (or one map of a `frame_depth_sink`) of a result that is rescaled by the metric-depth
     factor `s` the way `FilledReturn.scale` does it (disparities / s, translations * s): depths * s.  `run` itself
     applies no metric rescaling, so the maps are in the trajectory's units until this is applied.  -> a new tensor of
-    the same dtype (fp16 maps are scaled in fp32 and rounded once)."""
+    the same dtype (fp16 maps are scaled in fp32 and rounded once).  It fits `SLAMOutput.fused_depths` (and the maps of
+    a `fused_depth_sink`) as it is: they are depths in the same units, and an empty pixel's 0 stays 0."""
     return (frame_depths.float() * s).to(frame_depths.dtype)
 
 
@@ -113,6 +114,38 @@ class FusedCloud:
     def voxel_index(self):
         """-> int64 [M,3]: the voxels' integer coordinates, decoded from `key`"""
         return torch.stack([((self.key >> (21 * i)) & 0x1FFFFF) - (1 << 20) for i in range(3)], dim=1)
+
+    def render(self, cams_w2c, intrinsics, camera, size_or_resize, point_size=None, max_radius=2, dtype=torch.float16,
+               color=True, want_index=False):
+        """The cloud seen from B cameras: one `ingest.cloud_render` and one `ingest.cloud_resolve` launch ->
+        (depth [B,H0,W0] of `dtype`, rgb [B,H0,W0,3] uint8 or None, index [B,H0,W0] int32 or None).  Per pixel the
+        nearest point whose square footprint covers it - z for pinhole / MEI, the range for the panorama, in the units
+        of `xyz` - 0 where nothing is drawn; with `color` (and a coloured cloud) that point's colour, with `want_index`
+        its row in this cloud (-1 where nothing is drawn).
+
+        cams_w2c [B,7] fp32 world -> camera rows (rig[v]^-1 G[f]); intrinsics [B,4] ([B,5] MEI) at SLAM resolution, or
+        one row for all images; camera "pinhole" / "mei" / "panorama"; size_or_resize (H, W) - images at SLAM
+        resolution - or the clip's `StandardResize` - images at the native size, pixel for pixel beside `frame_depths`;
+        point_size the points' edge length (default: `voxel`); max_radius 0 to 4 pixels.  A cloud rescaled with
+        `rescale_fused_cloud` renders depths in the rescaled units when it is given the rescaled cameras."""
+        from . import ingest
+        require(torch.is_tensor(cams_w2c) and cams_w2c.dim() == 2 and cams_w2c.shape[1] == 7, "cams_w2c: [B,7]")
+        dev, B = self.xyz.device, int(cams_w2c.shape[0])
+        intrinsics = torch.as_tensor(intrinsics, dtype=torch.float32, device=dev)
+        if intrinsics.dim() == 1:
+            intrinsics = intrinsics[None]
+        require(intrinsics.dim() == 2 and intrinsics.shape[0] in (1, B), "intrinsics: one row, or one per image")
+        require(size_or_resize is not None, "size_or_resize: (H, W) or a StandardResize")
+        geom = ingest.render_params(size_or_resize)
+        require(point_size is None or float(point_size) >= 0, "point_size: a length, not negative")
+        if not self.xyz.is_cuda:
+            raise NotImplementedError("FusedCloud.render: the cloud must live on the device (vipe_cloud_render is a HIP kernel)")
+        zbuf = ingest.cloud_zbuffer(B, geom[6], geom[7], dev)
+        ingest.cloud_render(self.xyz.contiguous(), cams_w2c.to(device=dev, dtype=torch.float32).contiguous(),
+                            intrinsics.expand(B, -1).contiguous(), camera, geom, zbuf,
+                            self.voxel if point_size is None else point_size, max_radius=max_radius)
+        rgb = self.rgb.contiguous() if color and self.rgb is not None else None
+        return ingest.cloud_resolve(zbuf, rgb, dtype=dtype, want_index=want_index)
 
 
 def rescale_fused_cloud(cloud, s):
@@ -162,11 +195,18 @@ class SLAMOutput:
 
     None unless `SLAMConfig.fused_cloud`: `fused_cloud`, a `FusedCloud` - the confident pixels of all those maps in one
     voxel-fused, coloured point cloud of bounded size (`rescale_fused_cloud` for a metric factor,
-    `driver.artifacts.write_ply` for a file)."""
+    `driver.artifacts.write_ply` for a file).
+
+    None unless `SLAMConfig.fused_depth` (and no `fused_depth_sink`): `fused_depths` [T,V,H0,W0]
+    (`SLAMConfig.frame_depth_dtype`), pixel for pixel beside `frame_depths`: the fused cloud drawn into every frame's
+    camera with the final poses (`FusedCloud.render`), 0 where nothing is drawn, in the trajectory's units
+    (`rescale_frame_depths` for a metric factor); with `SLAMConfig.fused_depth_color` `fused_rgb` [T,V,H0,W0,3] uint8, the
+    colour of the point each pixel shows."""
 
     def __init__(self, *, trajectory, intrinsics, rig=None, slam_map=None, ba_residual=0.0, keyframe_disps_up=None,
                  keyframe_disps_up_valid=None, keyframe_disp_var=None, keyframe_pose_cov=None, frame_depths=None,
-                 frame_disps_lowres=None, frame_depth_conf=None, fused_cloud=None):
+                 frame_disps_lowres=None, frame_depth_conf=None, fused_cloud=None, fused_depths=None, fused_rgb=None):
+        self.fused_depths, self.fused_rgb = fused_depths, fused_rgb
         self.frame_depths, self.frame_disps_lowres = frame_depths, frame_disps_lowres
         self.frame_depth_conf, self.fused_cloud = frame_depth_conf, fused_cloud
         self.keyframe_disp_var, self.keyframe_pose_cov = keyframe_disp_var, keyframe_pose_cov

@@ -86,6 +86,14 @@ class SLAMConfig:
                                            # and `FusedCloud.stats` says how many
     fused_cloud_min_count: int = 2         # points a voxel needs to be extracted
     fused_cloud_color: bool = True         # mean colour per voxel from the frames handed to `run`
+    fused_depth: bool = False      # the fused cloud drawn back into every frame and view (`SLAMOutput.fused_depths`, DESIGN
+                                   # 19): after the extraction, per pass-2 chunk of frames one `vipe_cloud_render` and one
+                                   # `vipe_cloud_resolve` launch with the final poses, on the grid of `frame_depths`.  Needs
+                                   # `fused_cloud`.  It only reads.  Off: nothing is allocated, no launch differs
+    fused_depth_max_radius: int = 2        # largest footprint radius in pixels (0 to 4); a point covers its voxel's size
+    fused_depth_color: bool = False        # `SLAMOutput.fused_rgb` beside the maps (needs `fused_cloud_color`)
+    fused_depth_sink: object = None        # callable (frame_idx, view_idx, depth [H0,W0] device tensor), in frame order
+                                           # (`driver.artifacts.DepthZipWriter`); `fused_depths` then stays None
     sparse_tracks: str = None     # "klt": `run` builds a `KLTSparseTracks(n_views)` (corners + pyramidal Lucas-Kanade in
                                    # HIP) when the caller passed no tracker - the motion filter's track score and the BA's
                                    # track term get real tracks.  None: no tracker is built, nothing is launched or changed
@@ -130,6 +138,12 @@ class SLAMSystem:
             cap = int(c.fused_cloud_capacity)
             assert 0 < cap <= 1 << 30 and cap & (cap - 1) == 0, "SLAMConfig.fused_cloud_capacity: a power of two, at most 2^30"
             assert int(c.fused_cloud_min_count) >= 1, "SLAMConfig.fused_cloud_min_count: at least 1"
+        if self.config.fused_depth:
+            c = self.config
+            assert c.fused_cloud, "SLAMConfig.fused_depth draws the cloud of fused_cloud: set fused_cloud=True as well"
+            assert 0 <= int(c.fused_depth_max_radius) <= 4, "SLAMConfig.fused_depth_max_radius: 0 to 4"
+            assert not c.fused_depth_color or c.fused_cloud_color, \
+                "SLAMConfig.fused_depth_color shows the cloud's colours: set fused_cloud_color=True as well"
         self._config_tracker = sparse_tracks is None and self.config.sparse_tracks == "klt"  # then a fresh one per run
         self._resizes = None  # one `StandardResize` per view inside `run(..., native_resolution=True)`, None outside it
         # system.py:91 builds a tracker from the config; here the caller's (`track_image(frames)` per frame of pass 1,
@@ -419,6 +433,42 @@ class SLAMSystem:
                                                        color=c.fused_cloud_color)
         return FusedCloud(xyz, rgb, count, key, c.fused_cloud_voxel, table[2].tolist())
 
+    def _render_fused_depths(self, cloud, poses, resizes):
+        """`SLAMConfig.fused_depth`, after `_extract_cloud`: the cloud drawn into every frame and view with the final
+        world -> camera poses rig[v]^-1 G[f] (composed on the device), on the grid of `frame_depths` - the native size
+        with native_resolution, SLAM resolution otherwise.  Per pass-2 chunk of frames ONE `cloud_render` and ONE
+        `cloud_resolve` launch over a z-buffer of that chunk's images.  -> (fused_depths [T,V,H0,W0] or None when the maps
+        went to `fused_depth_sink`, fused_rgb [T,V,H0,W0,3] uint8 or None)"""
+        from . import ingest
+        b, c = self.buffer, self.config
+        V, T = b.n_views, int(poses.data.shape[0])
+        cams = torch.stack([(SE3(b.rig[v][None]).inv() * poses).data for v in range(V)], dim=1).float().contiguous()  # [T,V,7]
+        geom = ingest.render_params(resizes[0] if resizes is not None else (b.height, b.width))
+        H0, W0 = geom[6:]
+        chunk = max(1, int(c.infill.infill_chunk_size))
+        rgb_points = cloud.rgb.contiguous() if c.fused_depth_color else None
+        depths = rgbs = None
+        if c.fused_depth_sink is None:
+            depths = torch.empty((T, V, H0, W0), dtype=c.frame_depth_dtype, device=self.device)
+        if c.fused_depth_color:
+            rgbs = torch.empty((T, V, H0, W0, 3), dtype=torch.uint8, device=self.device)
+        xyz = cloud.xyz.contiguous()
+        for c0 in range(0, T, chunk):
+            n = min(chunk, T - c0)
+            zbuf = ingest.cloud_zbuffer(n * V, H0, W0, self.device)
+            ingest.cloud_render(xyz, cams[c0:c0 + n].view(n * V, 7), b.intrinsics.repeat(n, 1), b.camera_type, geom, zbuf,
+                                cloud.voxel, max_radius=c.fused_depth_max_radius)
+            depth, rgb, _ = ingest.cloud_resolve(zbuf, rgb_points, dtype=c.frame_depth_dtype)
+            if depths is not None:
+                depths[c0:c0 + n] = depth.view(n, V, H0, W0)
+            if rgbs is not None:
+                rgbs[c0:c0 + n] = rgb.view(n, V, H0, W0, 3)
+            if c.fused_depth_sink is not None:
+                for j in range(n):
+                    for v in range(V):
+                        c.fused_depth_sink(c0 + j, v, depth[j * V + v])
+        return depths, rgbs
+
     def _check_camera(self, camera_type, frames, native_resolution):
         """What a camera model rules out, before anything is built or touches the device.  The panorama
         (cameras.py:357-396) is the whole sphere on an equirectangular frame: no intrinsics (all-zero rows, as the
@@ -491,7 +541,13 @@ class SLAMSystem:
         maps that at least `fused_cloud_min_agree` keyframes confirm, back-projected to the world and merged per voxel of
         `fused_cloud_voxel` (centroid, mean colour of the frames' `rgb`, count), voxels with fewer than
         `fused_cloud_min_count` points left out, sorted by voxel key.  The table has `fused_cloud_capacity` slots and does
-        not grow: `fused_cloud.stats` counts what it dropped.  It only reads as well."""
+        not grow: `fused_cloud.stats` counts what it dropped.  It only reads as well.
+
+        With `SLAMConfig.fused_depth` on top of that, `fused_depths` [T,V,H0,W0] (`frame_depth_dtype`) lies pixel for pixel
+        beside `frame_depths`: that cloud drawn back into every frame and view with the final poses (`FusedCloud.render`'s
+        rule: the nearest point whose footprint covers the pixel, 0 where none does) - one surface for the whole clip,
+        gated by confidence already - and with `fused_depth_color` `fused_rgb` [T,V,H0,W0,3] uint8; or every map goes to
+        `SLAMConfig.fused_depth_sink` and `fused_depths` stays None.  It only reads."""
         frames = [f if isinstance(f, (list, tuple)) else [f] for f in frames]
         total, n_views = len(frames), len(frames[0])
         assert total > 0 and all(len(f) == n_views for f in frames)
@@ -550,4 +606,7 @@ class SLAMSystem:
             self.frame_depth_conf = None
         if self.config.fused_cloud:
             up.update(fused_cloud=self._extract_cloud())
+        if self.config.fused_depth:
+            fused_depths, fused_rgb = self._render_fused_depths(up["fused_cloud"], filled.poses, resizes)
+            up.update(fused_depths=fused_depths, fused_rgb=fused_rgb)
         return SLAMOutput(trajectory=filled.poses.inv(), intrinsics=intrinsics, rig=SE3(b.rig.clone()), slam_map=slam_map, **up)
