@@ -513,9 +513,20 @@ int vipe_conv_packed_dims(int Cout, int Cin, int KH, int KW, int* cout_pad, int*
  *             channels starts from (d_accinit of that launch, mode | VIPE_CONV_ACCINIT_F32).  Cout % 4 == 0; same shape
  *             support as d_accinit.  Used to compute the hidden-state part of the z|r gates of the NEXT update
  *             iteration on a side stream while the dense BA of the current one leaves the chip idle.
+ *   7 HEADS_FUSED  Cin = 128, Cout = 256, 3x3, relu, H % 4 == 0 and W % 64 == 0 (VIPE_EUNSUPPORTED otherwise): the
+ *             convolution delta0 | weight0 with the 3x3 flow / weight heads (mode 4 over its output) contracted in its
+ *             epilogue - nothing of the 256 channels is stored.  d_net = the heads2 weights as matrix fragments
+ *             (fp16 [cout slice s = 2][cout half h = 2][row block rb = 2][ip = 2][lane = 64][e = 8]: the weight
+ *             of output 2 s + o, tap t, with 2 t + o = 16 rb + lane % 16 (zero from 18 on), for input channel
+ *             128 s + 64 h + 32 ip + 16 (e / 4) + 4 (lane / 16) + e % 4), d_fout = [B*H*W, 4] f32 and
+ *             d_y2 = [vipe_heads_border_floats] f32 receive every tile's partial sums; vipe_heads_finish on the same
+ *             stream turns d_fout into the output of mode 4.  All sums in a fixed order, no atomics: run to run
+ *             bit-identical; against the two launches it replaces, the fp32 summation order before the one fp16
+ *             rounding differs.
  * mode may be OR-ed with VIPE_CONV_ACCINIT_F32: d_accinit is then float32 [B*H*W, ai_ctot] instead of fp16.
  */
 #define VIPE_CONV_PARTIAL 6
+#define VIPE_CONV_HEADS_FUSED 7
 #define VIPE_CONV_ACCINIT_F32 0x100
 /* d_accinit (optional, fp16 [B*H*W, ai_ctot], channels [ai_coff, ai_coff + Cout)): initial value of the accumulators,
  * i.e. a precomputed partial sum over OTHER input channels (convolution is linear in its input channels).  Used to
@@ -528,8 +539,18 @@ int vipe_conv2d_fused(const void* d_x0, int x0_ctot, int x0_coff, const void* d_
                       const void* d_accinit, int ai_ctot, int ai_coff, int B, int H, int W, int Cin, int Cout, int KH,
                       int KW, int act, int mode, void* stream);
 
-/* [fused] the whole flow-update operator (UpdateModule.forward, droid_net.py:467-499) sequenced natively: the 13 fused
- * convolutions above + vipe_corr_lookup_conv1x1 + vipe_segment_mean_nhwc_f16 + the pooled-context product in ONE call
+/* [fused] mode 7 of vipe_conv2d_fused and its second half.  vipe_heads_fused_ok: 1 when the operator (in its two-stream form) takes
+ * the fused pair on an H x W grid (4 x 64 tiles; VIPE_AMD_FUSED_HEADS=0 in the environment switches it off for A/B runs) - the one
+ * predicate of the library and of its Python sequencer.  vipe_heads_border_floats: size of d_border.  vipe_heads_finish:
+ * d_dw[m] (the pixel's own partial sums) + its neighbouring tiles' border sums + d_bias[0..3], rounded as mode 4 does. */
+int vipe_heads_fused_ok(int H, int W);
+int vipe_heads_border_floats(int E, int H, int W, int64_t* n_floats);
+int vipe_heads_finish(float* d_dw, const float* d_border, const float* d_bias, int E, int H, int W, void* stream);
+
+/* [fused] the whole flow-update operator (UpdateModule.forward, droid_net.py:467-499) sequenced natively: its fused
+ * convolutions above (eleven launches: corr0 - or the fused lookup -, corr2, flow0, flow2, w, z|r, q, heads0, heads2,
+ * agg2, eta; twelve with heads0 split by consumer, see vipe_update_weights; one more z|r launch with a partly staged
+ * gate state) + vipe_corr_lookup_conv1x1 + vipe_segment_mean_nhwc_f16 + the pooled-context product in ONE call
  * (issued one by one from the host each launch costs more than most of them run for on a frontend window).
  * All tensors channels-last fp16 unless noted; the weight descriptors are `vipe_conv_pack_weights` outputs + fp32 biases
  * (each readable up to its convolution's padded output-channel count, see d_bias above). */
@@ -540,6 +561,16 @@ typedef struct {
   const float *corr0_b, *corr2_b, *flow0_b, *flow2_b, *gw_b, *zr_b, *q_b, *heads0_b, *heads2_b, *agg2_b, *eta_b;
   const float* glo_wT; /* [128,384] f32: (convz_glo | convr_glo | convq_glo) weights transposed */
   const float* glo_b;  /* [384] */
+  /* heads0 packed twice more, by consumer: agg1 [128 <- 128] = its channels 256..383 (GraphAgg's first convolution) and
+     heads_dw [256 <- 128] = its channels 0..255 (delta0 | weight0).  Both set, a side stream and n_src > 0: the operator
+     runs agg1 first, so that the GraphAgg chain (segmented mean, agg conv 2, eta) starts beside the heads convolution
+     instead of behind all 384 channels.  Otherwise: the one 384-channel heads0 launch (three launches of 128 and 256
+     channels leave more partly filled workgroup rounds than one of 384), then heads || GraphAgg chain. */
+  const void *agg1_w, *heads_dw_w;
+  const float *agg1_b, *heads_dw_b;
+  const void* heads2_frag; /* optional: heads2_w as the matrix fragments of vipe_conv2d_fused mode 7.  With it (and agg1_w,
+                              heads_dw_w, vipe_update_buffers.hborder) the split form takes the fused heads on grids
+                              of 4 x 64 tiles: hbuf[..., 0:256] is then not written */
 } vipe_update_weights;
 typedef struct {
   int E, H, W, n_src;        /* edges, grid, source nodes (0: no GraphAgg / eta) */
@@ -562,7 +593,7 @@ typedef struct {
   void *agg, *a2;            /* scratch [n_src,H,W,128] */
   float* eta;                /* out [n_src,H,W] f32 */
   void* side_stream;         /* optional second stream: the operator's two pairs of independent chains - (lookup + corr
-                                encoder) || (flow encoder), and (flow / weight heads) || (GraphAgg mean, agg conv 2, eta) -
+                                encoder) || (flow encoder), and (flow / weight heads) || (GraphAgg mean, agg conv 2, eta; from behind agg1 when heads0 is split by consumer) -
                                 are issued on `stream` and on this one, forked and joined with events inside the call
                                 (a gather-bound kernel next to a matrix-bound one); NULL: everything on `stream` */
   float* pzr;                /* optional [gate_state,H,W,256] f32: hidden-state part of the z|r gates (vipe_update_gate_state) */
@@ -570,6 +601,7 @@ typedef struct {
                                 of the gates for `net` (vipe_update_gate_state ran on it): the operator skips the
                                 global-context stage, and the z|r convolution of the first n edges runs over (corr | flow)
                                 only, its accumulators starting from pzr; edges [n, E) take the unsplit convolution */
+  float* hborder;            /* optional scratch [vipe_heads_border_floats(E, H, W)] f32 for the fused heads */
 } vipe_update_buffers;
 int vipe_update_operator(const vipe_update_weights* weights, const vipe_update_buffers* buffers, void* stream);
 

@@ -30,7 +30,7 @@ typedef _Float16 half4 __attribute__((ext_vector_type(4)));
 typedef float float16v __attribute__((ext_vector_type(16)));
 typedef float float4v __attribute__((ext_vector_type(4)));
 
-enum Epi { EPI_PLAIN = 0, EPI_GLO = 1, EPI_ZR = 2, EPI_Q = 3, EPI_HEADS = 4, EPI_ETA = 5, EPI_PARTIAL = 6 };
+enum Epi { EPI_PLAIN = 0, EPI_GLO = 1, EPI_ZR = 2, EPI_Q = 3, EPI_HEADS = 4, EPI_ETA = 5, EPI_PARTIAL = 6, EPI_HEADS_FUSED = 7 };
 
 struct ConvArgs {
   const half_t* x0; int x0_ctot, x0_coff;  // input channels [0, split)
@@ -50,6 +50,9 @@ struct ConvArgs {
   float* fout;                                 // GLO: glo_sum [B,Cout]; HEADS: [M,4]; ETA: [M]
   const half_t* accinit; int ai_ctot, ai_coff;  // optional initial accumulator [M, ai_ctot] (a partial conv sum)
   int ai_f32;                                   // ... held as fp32 (the output of an EPI_PARTIAL launch) instead of fp16
+  // EPI_HEADS_FUSED: the 3x3 heads2 weights as MFMA A fragments (layout: include/vipe_amd.h, mode 7) and the per-tile border sums
+  const half_t* w2;
+  float* border;                                // [tiles][HB_N][4]
   // flat tiling (FLAT kernels, any H x W): a tile is 256 consecutive positions q = y * Wp + x of the image padded to
   // pitch Wp = W + pad columns (zeros); filled by launch_conv
   int f_wp, f_hwp, f_tiles, f_pieces, f_xbytes, f_p1lo, f_p1hi;
@@ -443,8 +446,17 @@ __device__ __forceinline__ int flat_pixel(int q, int e, int H, int W, int wp, in
   return x < W ? (e * H + y) * W + x : -1;
 }
 
+// EPI_HEADS_FUSED: the ring of positions around a 4 x 64 tile, as one record per tile - top row (py = -1, px = -1..64),
+// bottom row (py = 4), left column (px = -1, py = 0..3), right column (px = 64)
+constexpr int HB_N = 2 * (HALO_TW + 2) + 2 * HALO_TH;  // 140
+constexpr int HG_PITCH = HALO_TH * HALO_TW + 4;         // floats per g row in LDS: the four k-groups' rows hit distinct banks
+__host__ __device__ __forceinline__ int hb_index(int py, int px) {
+  return py < 0 ? px + 1 : py >= HALO_TH ? (HALO_TW + 2) + px + 1 : px < 0 ? 2 * (HALO_TW + 2) + py : 2 * (HALO_TW + 2) + HALO_TH + py;
+}
+
 // VAR: 0 = the general kernel; 1 = initial accumulators held as fp32 (a.ai_f32); 2 = EPI_PARTIAL (raw fp32 accumulators
-// out).  Separate instantiations: folded into the general one as run-time branches they cost it 75 spilled VGPRs.
+// out); 3 = EPI_HEADS_FUSED (the 3x3 flow / weight heads contracted from the accumulators, nothing of the tile stored).
+// Separate instantiations: folded into the general one as run-time branches they cost it 75 spilled VGPRs.
 // FLAT: any H x W.  The image is taken with one zero column appended to every row (pitch Wp = W + 1; a 1x1 needs none)
 // and flattened: position q = y * Wp + x.  A tile is 256 CONSECUTIVE positions of one image, so tap (dy, dx) of every
 // position is the position dy * Wp + dx further on - one shifted window of a single run of 256 + 2 Wp + 2 halo rows in
@@ -714,6 +726,72 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
         }
         return;
       }
+    }
+    if constexpr (VAR == 3) {
+      // delta0 | weight0 -> heads2 without the round trip through hbuf.  heads2 is block diagonal: its outputs 2s, 2s + 1
+      // read only the 128 channels of cout slice s, which this workgroup holds for its 4 x 64 pixels.  relu(conv + bias)
+      // is rounded to fp16 exactly as stage_all would store it; a lane's 4 + 4 channels of two adjacent 16-cout blocks
+      // are the 8 k-values of a 16x16x32 B fragment (the k order within the instruction is free: the host lays the
+      // heads2 weights out in the same order, a.w2), so g[tap, o][pixel] = sum over the wave's 64 channels is 16
+      // matrix instructions.  The two cout halves and the taps are then summed in ONE fixed order through LDS: each
+      // thread forms the output of one position of the dilated 6 x 66 tile from the taps whose source pixel lies in
+      // this tile.  Own pixels go to fout[M,4] (columns 2s, 2s + 1), positions in the ring around the tile to this
+      // tile's border record; heads_finish_kernel adds a pixel's own sum and its neighbours' border sums.  No atomics.
+      // (A third cout slice with the plain epilogue in the same instantiation - all of heads0 in one launch - was
+      // tried: 144 bytes of scratch per lane, reloaded inside the K loop.)
+      static_assert(BMC == 128 && KS == 3 && !FLAT, "the fused heads exist for the aligned 128-cout 3x3 tile only");
+      const int slice = cout0 >> 7;
+      float* G = reinterpret_cast<float*>(lds);  // [cout half][18 = tap * 2 + o][HG_PITCH]
+      float4 bq[MI];
+#pragma unroll
+      for (int i = 0; i < MI; ++i) bq[i] = *reinterpret_cast<const float4*>(a.bias + cout0 + wm * 64 + i * 16 + 4 * lk);
+      const half8* af = reinterpret_cast<const half8*>(a.w2) + (slice * 2 + wm) * 4 * 64 + lane;  // [16-row block][cout pair][lane]
+      half8 afr[2][2];
+#pragma unroll
+      for (int q = 0; q < 4; ++q) afr[q >> 1][q & 1] = af[q * 64];
+#pragma unroll
+      for (int j = 0; j < NJ; ++j) {
+        half8 hb[2];
+#pragma unroll
+        for (int i = 0; i < MI; ++i) {
+          hb[i >> 1][(i & 1) * 4 + 0] = (half_t)fmaxf(acc16[i][j][0] + bq[i].x, 0.0f);
+          hb[i >> 1][(i & 1) * 4 + 1] = (half_t)fmaxf(acc16[i][j][1] + bq[i].y, 0.0f);
+          hb[i >> 1][(i & 1) * 4 + 2] = (half_t)fmaxf(acc16[i][j][2] + bq[i].z, 0.0f);
+          hb[i >> 1][(i & 1) * 4 + 3] = (half_t)fmaxf(acc16[i][j][3] + bq[i].w, 0.0f);
+        }
+        float4v g0 = float4v{0.0f, 0.0f, 0.0f, 0.0f}, g1 = g0;
+        g0 = __builtin_amdgcn_mfma_f32_16x16x32_f16(afr[0][0], hb[0], g0, 0, 0, 0);
+        g0 = __builtin_amdgcn_mfma_f32_16x16x32_f16(afr[0][1], hb[1], g0, 0, 0, 0);
+        g1 = __builtin_amdgcn_mfma_f32_16x16x32_f16(afr[1][0], hb[0], g1, 0, 0, 0);
+        g1 = __builtin_amdgcn_mfma_f32_16x16x32_f16(afr[1][1], hb[1], g1, 0, 0, 0);
+        const int p = wn * 64 + j * 16 + l16;
+#pragma unroll
+        for (int r = 0; r < 4; ++r) G[(wm * 18 + 4 * lk + r) * HG_PITCH + p] = g0[r];
+        if (lk == 0) {
+          G[(wm * 18 + 16) * HG_PITCH + p] = g1[0];
+          G[(wm * 18 + 17) * HG_PITCH + p] = g1[1];
+        }
+      }
+      __syncthreads();
+      for (int idx = tid; idx < 6 * 66 * 2; idx += 512) {
+        const int o = idx & 1, pos = idx >> 1, py = pos / 66 - 1, px = pos % 66 - 1;
+        const int yy = y0 + py, xx = x0 + px;
+        if (yy < 0 || yy >= a.H || xx < 0 || xx >= a.W) continue;  // outside the image: dropped
+        float sum = 0.0f;
+#pragma unroll
+        for (int tap = 0; tap < 9; ++tap) {
+          const int sy = py + tap / 3 - 1, sx = px + tap % 3 - 1;  // the source pixel of this tap
+          if ((unsigned)sy < (unsigned)HALO_TH && (unsigned)sx < (unsigned)HALO_TW) {
+            const float* gp = G + (tap * 2 + o) * HG_PITCH + sy * HALO_TW + sx;
+            sum += gp[0] + gp[18 * HG_PITCH];
+          }
+        }
+        if ((unsigned)py < (unsigned)HALO_TH && (unsigned)px < (unsigned)HALO_TW)
+          a.fout[((int64_t)(e * a.H + yy) * a.W + xx) * 4 + slice * 2 + o] = sum;
+        else
+          a.border[((int64_t)tile * HB_N + hb_index(py, px)) * 4 + slice * 2 + o] = sum;
+      }
+      return;
     }
     constexpr int PITCH = BMC + 8;  // halves per staged pixel
     half_t* stage = reinterpret_cast<half_t*>(lds);
@@ -1255,6 +1333,38 @@ VIPE_EXPORT int vipe_conv_pack_weights(const void* d_w_oihw, void* d_w_packed, i
 
 namespace {
 
+// EPI_HEADS_FUSED, second half: dw[m] = heads epilogue of (the pixel's own sum, left in dw by its tile) + (the border sums
+// of the at most three neighbouring tiles whose ring covers it), in one fixed order; the rounding of EPI_HEADS
+__global__ __launch_bounds__(256) void heads_finish_kernel(float* __restrict__ dw, const float* __restrict__ border,
+                                                           const float* __restrict__ bias, int64_t M, int H, int W) {
+  const int64_t m = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (m >= M) return;
+  const int x = (int)(m % W), y = (int)((m / W) % H), e = (int)(m / ((int64_t)W * H));
+  const int xsegs = W / HALO_TW, ysegs = H / HALO_TH;
+  const int ty = y / HALO_TH, tx = x / HALO_TW, py = y % HALO_TH, px = x % HALO_TW;
+  const int tile = (e * ysegs + ty) * xsegs + tx;
+  float4 s = reinterpret_cast<const float4*>(dw)[m];
+  auto add = [&](int t, int bi) {
+    const float4 v = reinterpret_cast<const float4*>(border)[(int64_t)t * HB_N + bi];
+    s.x += v.x; s.y += v.y; s.z += v.z; s.w += v.w;
+  };
+  const bool up = py == 0 && ty > 0, down = py == HALO_TH - 1 && ty < ysegs - 1;
+  const bool left = px == 0 && tx > 0, right = px == HALO_TW - 1 && tx < xsegs - 1;
+  // this pixel in the neighbour's tile coordinates
+  if (up) add(tile - xsegs, hb_index(HALO_TH, px));
+  if (down) add(tile + xsegs, hb_index(-1, px));
+  if (left) add(tile - 1, hb_index(py, HALO_TW));
+  if (right) add(tile + 1, hb_index(py, -1));
+  if (up && left) add(tile - xsegs - 1, hb_index(HALO_TH, HALO_TW));
+  if (up && right) add(tile - xsegs + 1, hb_index(HALO_TH, -1));
+  if (down && left) add(tile + xsegs - 1, hb_index(-1, HALO_TW));
+  if (down && right) add(tile + xsegs + 1, hb_index(-1, -1));
+  const float4 b = *reinterpret_cast<const float4*>(bias);
+  const float v0 = s.x + b.x, v1 = s.y + b.y, v2 = s.z + b.z, v3 = s.w + b.w;
+  reinterpret_cast<float4*>(dw)[m] = make_float4((float)(half_t)v0, (float)(half_t)v1, (float)(half_t)act_apply(v2, VIPE_ACT_SIGMOID),
+                                                 (float)(half_t)act_apply(v3, VIPE_ACT_SIGMOID));
+}
+
 // one hipFuncSetAttribute per (kernel, device): the dynamic-LDS ceiling of every kernel that may ask for > 64 KiB
 template <typename K>
 void allow_lds(K kernel, std::atomic<uint64_t>& seen, size_t bytes) {
@@ -1278,7 +1388,7 @@ bool flat_geometry(ConvArgs& a, int pad) {
 }
 
 // this call needs a tile kernel (initial accumulators, raw partial sums): the gather kernels are no fallback for it
-inline bool needs_tile_kernel(const ConvArgs& a) { return a.accinit || a.epi == EPI_PARTIAL || a.ai_f32; }
+inline bool needs_tile_kernel(const ConvArgs& a) { return a.accinit || a.epi == EPI_PARTIAL || a.ai_f32 || a.epi == EPI_HEADS_FUSED; }
 
 template <int BMC, int KS, int VAR, bool FLAT>
 int launch_halo32(const ConvArgs& a, int tiles, int gy, size_t lds, hipStream_t s) {
@@ -1293,6 +1403,11 @@ int launch_halo_family(ConvArgs& a, int cp, int64_t M, hipStream_t s) {
   const bool split_ok = a.split >= a.Cin || a.split % H32_BK == 0;
   const int tiles = FLAT ? a.B * a.f_tiles : (int)(M / (HALO_TH * HALO_TW));
   const size_t xb = FLAT ? (size_t)a.f_xbytes : (size_t)H32_XBYTES;
+  if (a.epi == EPI_HEADS_FUSED) {
+    // the aligned 128 -> 256 3x3 with the heads contracted in its epilogue (validated by vipe_conv2d_fused)
+    if constexpr (FLAT) return VIPE_EUNSUPPORTED;
+    else return launch_halo32<128, 3, 3, false>(a, tiles, 2, 3 * (size_t)128 * 64 + 2 * xb + 1024, s);
+  }
   if (needs_tile_kernel(a)) {
     // initial accumulators / raw partial sums: the 16x16x32 halo kernel with >= 64 output channels (fp32 initial
     // accumulators and partial sums: 3x3, >= 128 output channels)
@@ -1460,7 +1575,12 @@ VIPE_EXPORT int vipe_conv2d_fused(const void* d_x0, int x0_ctot, int x0_coff, co
   }
   const int ai_f32 = (mode & VIPE_CONV_ACCINIT_F32) != 0;
   mode &= ~VIPE_CONV_ACCINIT_F32;
-  VIPE_CHECK_ARG(mode >= EPI_PLAIN && mode <= EPI_PARTIAL);
+  VIPE_CHECK_ARG(mode >= EPI_PLAIN && mode <= EPI_HEADS_FUSED);
+  if (mode == EPI_HEADS_FUSED) {
+    VIPE_CHECK_ARG(d_fout && d_net && d_y2 && Cin == 128 && Cout == 256 && KH == 3 && KW == 3 && act == VIPE_ACT_RELU &&
+                   !d_extra && !d_accinit && !ai_f32 && split >= Cin);
+    if (H % HALO_TH != 0 || W % HALO_TW != 0) return VIPE_EUNSUPPORTED;
+  }
   if (mode == EPI_PARTIAL) VIPE_CHECK_ARG(d_fout && y_ctot % 4 == 0 && y_coff % 4 == 0 && y_coff + Cout <= y_ctot && !d_extra);
   if (mode == EPI_PLAIN) VIPE_CHECK_ARG(d_y && y_ctot % 4 == 0 && y_coff % 4 == 0);
   if (mode == EPI_GLO) VIPE_CHECK_ARG(d_net && d_fout);
@@ -1475,12 +1595,37 @@ VIPE_EXPORT int vipe_conv2d_fused(const void* d_x0, int x0_ctot, int x0_coff, co
   a.w = (const half_t*)d_w_packed; a.bias = d_bias; a.extra = d_extra; a.extra_stride = extra_stride; a.extra_off = extra_off;
   a.y = (half_t*)d_y; a.y_ctot = y_ctot; a.y_coff = y_coff;
   a.y2 = (half_t*)d_y2; a.y2_ctot = y2_ctot; a.y2_coff = y2_coff;
+  if (mode == EPI_HEADS_FUSED) {
+    a.w2 = (const half_t*)d_net; a.border = (float*)d_y2;
+    d_net = nullptr; a.y2 = nullptr;
+  }
   a.net = (const half_t*)d_net; a.net_ctot = net_ctot; a.net_coff = net_coff;
   a.zbuf = (const half_t*)d_z; a.fout = d_fout;
   a.accinit = (const half_t*)d_accinit; a.ai_ctot = ai_ctot; a.ai_coff = ai_coff; a.ai_f32 = ai_f32;
   a.B = B; a.H = H; a.W = W; a.Cin = Cin; a.Cout = Cout; a.KH = KH; a.KW = KW;
   a.act = act; a.epi = mode;
   return launch_conv(a, as_stream(stream));
+}
+
+VIPE_EXPORT int vipe_heads_fused_ok(int H, int W) {
+  const char* v = getenv("VIPE_AMD_FUSED_HEADS");  // read per call: a switch for A/B runs, not a hot path
+  const bool enabled = !(v && v[0] == '0');
+  return enabled && H > 0 && W > 0 && H % HALO_TH == 0 && W % HALO_TW == 0;
+}
+
+VIPE_EXPORT int vipe_heads_border_floats(int E, int H, int W, int64_t* n) {
+  VIPE_CHECK_ARG(n && E >= 0 && H > 0 && W > 0 && H % HALO_TH == 0 && W % HALO_TW == 0);
+  *n = (int64_t)E * (H / HALO_TH) * (W / HALO_TW) * HB_N * 4;
+  return VIPE_OK;
+}
+
+VIPE_EXPORT int vipe_heads_finish(float* d_dw, const float* d_border, const float* d_bias, int E, int H, int W, void* stream) {
+  VIPE_CHECK_ARG(E >= 0 && H > 0 && W > 0 && H % HALO_TH == 0 && W % HALO_TW == 0);
+  if (E == 0) return VIPE_OK;
+  VIPE_CHECK_ARG(d_dw && d_border && d_bias);
+  const int64_t M = (int64_t)E * H * W;
+  heads_finish_kernel<<<(unsigned)((M + 255) / 256), 256, 0, as_stream(stream)>>>(d_dw, d_border, d_bias, M, H, W);
+  return vipe_launch_status();
 }
 
 }  // extern "C"

@@ -1,6 +1,6 @@
 // The flow-update operator (UpdateModule.forward, vipe/slam/networks/droid_net.py:467-499) as ONE library call.
 //
-// The operator is 13 fused convolutions + a segmented mean + two small reductions (csrc/conv_mfma.hip, corr_lookup.hip,
+// The operator is a dozen fused convolutions + a segmented mean + two small reductions (csrc/conv_mfma.hip, corr_lookup.hip,
 // aux_ops.hip).  Issued one by one from Python each launch costs 10-15 us of argument marshalling, more than most of
 // these kernels run for on a frontend window (~48 edges): the keyframe frontend was launch bound (GPU idle 15-45 % of
 // the time, profiles/r02_video_*).  vipe_update_operator sequences them natively from two descriptor structs the host
@@ -69,8 +69,8 @@ VIPE_EXPORT int vipe_update_operator(const vipe_update_weights* wt, const vipe_u
     rc = (call);               \
     if (rc != VIPE_OK) return rc; \
   } while (0)
-  // two-stream form: s2 carries the flow encoder next to the lookup + correlation encoder, and the heads next to the
-  // GraphAgg chain
+  // two-stream form: s2 carries the flow encoder next to the lookup + correlation encoder, and the GraphAgg chain next
+  // to the heads
   hipStream_t s2 = (hipStream_t)b->side_stream;
   hipEvent_t* ev = s2 ? operator_events() : nullptr;
   if (s2 && !ev) return VIPE_EINVAL;
@@ -140,24 +140,51 @@ VIPE_EXPORT int vipe_update_operator(const vipe_update_weights* wt, const vipe_u
     RUN(vipe_conv2d_fused(b->rnet, 128, 0, b->xbuf, 320, 0, 128, wt->q_w, wt->q_b, b->extra, 384, 256, b->net_out, 128, 0, nullptr,
                           0, 0, b->net, 128, 0, b->zb, nullptr, nullptr, 0, 0, E, H, W, 448, 128, 3, 3, VIPE_ACT_NONE, 3, stream));
   }
-  // heads + first aggregation conv on net' (droid_net.py:486-487, 418)
-  RUN(vipe_conv2d_fused(b->net_out, 128, 0, nullptr, 0, 0, 128, wt->heads0_w, wt->heads0_b, nullptr, 0, 0, b->hbuf, 384, 0,
-                        nullptr, 0, 0, nullptr, 0, 0, nullptr, nullptr, nullptr, 0, 0, E, H, W, 128, 384, 3, 3, VIPE_ACT_RELU, 0,
-                        stream));
+  // heads + first aggregation conv on net' (droid_net.py:486-487, 418): hbuf = relu(delta0 | weight0 | agg1)
   const bool two_tails = s2 && b->n_src > 0;
-  if (two_tails) FORK(2);
-  RUN(vipe_conv2d_fused(b->hbuf, 384, 0, nullptr, 0, 0, 256, wt->heads2_w, wt->heads2_b, nullptr, 0, 0, nullptr, 0, 0, nullptr, 0,
-                        0, nullptr, 0, 0, nullptr, b->dw, nullptr, 0, 0, E, H, W, 256, 4, 3, 3, VIPE_ACT_NONE, 4,
-                        two_tails ? stream2 : stream));
-  if (b->n_src > 0) {
-    // scatter_mean over the edges of each source node (droid_net.py:420-421), agg conv 2, eta (:422-429)
+  const bool by_consumer = wt->agg1_w && wt->agg1_b && wt->heads_dw_w && wt->heads_dw_b;
+  auto heads0 = [&](const void* w, const float* bias, int coff, int cout) -> int {
+    return vipe_conv2d_fused(b->net_out, 128, 0, nullptr, 0, 0, 128, w, bias, nullptr, 0, 0, b->hbuf, 384, coff, nullptr, 0, 0,
+                             nullptr, 0, 0, nullptr, nullptr, nullptr, 0, 0, E, H, W, 128, cout, 3, 3, VIPE_ACT_RELU, 0, stream);
+  };
+  // scatter_mean over the edges of each source node (droid_net.py:420-421), agg conv 2, eta (:422-429)
+  auto agg_chain = [&](void* st) -> int {
+    if (b->n_src <= 0) return VIPE_OK;
     VIPE_CHECK_ARG(b->order && b->rowptr && b->agg && b->a2 && b->eta);
-    RUN(vipe_segment_mean_nhwc_f16(b->hbuf, 384, 256, b->order, b->rowptr, b->agg, b->n_src, (int64_t)H * W, 128, stream));
+    RUN(vipe_segment_mean_nhwc_f16(b->hbuf, 384, 256, b->order, b->rowptr, b->agg, b->n_src, (int64_t)H * W, 128, st));
     RUN(vipe_conv2d_fused(b->agg, 128, 0, nullptr, 0, 0, 128, wt->agg2_w, wt->agg2_b, nullptr, 0, 0, b->a2, 128, 0, nullptr, 0, 0,
-                          nullptr, 0, 0, nullptr, nullptr, nullptr, 0, 0, b->n_src, H, W, 128, 128, 3, 3, VIPE_ACT_RELU, 0,
-                          stream));
-    RUN(vipe_conv2d_fused(b->a2, 128, 0, nullptr, 0, 0, 128, wt->eta_w, wt->eta_b, nullptr, 0, 0, nullptr, 0, 0, nullptr, 0, 0,
-                          nullptr, 0, 0, nullptr, b->eta, nullptr, 0, 0, b->n_src, H, W, 128, 1, 3, 3, VIPE_ACT_NONE, 5, stream));
+                          nullptr, 0, 0, nullptr, nullptr, nullptr, 0, 0, b->n_src, H, W, 128, 128, 3, 3, VIPE_ACT_RELU, 0, st));
+    return vipe_conv2d_fused(b->a2, 128, 0, nullptr, 0, 0, 128, wt->eta_w, wt->eta_b, nullptr, 0, 0, nullptr, 0, 0, nullptr, 0, 0,
+                             nullptr, 0, 0, nullptr, b->eta, nullptr, 0, 0, b->n_src, H, W, 128, 1, 3, 3, VIPE_ACT_NONE, 5, st);
+  };
+  auto heads2 = [&](void* st) -> int {
+    return vipe_conv2d_fused(b->hbuf, 384, 0, nullptr, 0, 0, 256, wt->heads2_w, wt->heads2_b, nullptr, 0, 0, nullptr, 0, 0,
+                             nullptr, 0, 0, nullptr, 0, 0, nullptr, b->dw, nullptr, 0, 0, E, H, W, 256, 4, 3, 3, VIPE_ACT_NONE, 4, st);
+  };
+  if (by_consumer && two_tails) {
+    // heads0 split by consumer.  The GraphAgg chain needs only channels 256..383: they come first, and the chain runs
+    // on the side stream beside the 256 channels of the flow / weight heads instead of behind all 384.  Same kernels
+    // per 128-channel slice, so every result of the unfused heads is bit-identical to the one 384-channel launch.
+    RUN(heads0(wt->agg1_w, wt->agg1_b, 256, 128));
+    FORK(2);
+    RUN(agg_chain(stream2));
+    if (wt->heads2_frag && b->hborder && vipe_heads_fused_ok(H, W)) {
+      // grids of 4 x 64 tiles: heads2 contracted in the epilogue of delta0 | weight0 - hbuf[..., 0:256] is never written
+      RUN(vipe_conv2d_fused(b->net_out, 128, 0, nullptr, 0, 0, 128, wt->heads_dw_w, wt->heads_dw_b, nullptr, 0, 0, nullptr, 0, 0,
+                            b->hborder, 0, 0, wt->heads2_frag, 0, 0, nullptr, b->dw, nullptr, 0, 0, E, H, W, 128, 256, 3, 3,
+                            VIPE_ACT_RELU, VIPE_CONV_HEADS_FUSED, stream));
+      RUN(vipe_heads_finish(b->dw, b->hborder, wt->heads2_b, E, H, W, stream));
+    } else {
+      RUN(heads0(wt->heads_dw_w, wt->heads_dw_b, 0, 256));
+      RUN(heads2(stream));
+    }
+  } else {
+    // one stream (frontend windows, E < 64) or no chain: the one 384-channel launch - three launches of 128 + 256
+    // channels leave more partly filled workgroup rounds than one, with nothing to run beside them
+    RUN(heads0(wt->heads0_w, wt->heads0_b, 0, 384));
+    if (two_tails) FORK(2);
+    RUN(heads2(two_tails ? stream2 : stream));
+    RUN(agg_chain(stream));
   }
   if (two_tails) JOIN(3);
 #undef FORK

@@ -6,15 +6,17 @@ of the reference (`cat[net, inp, corr_feat, flow_feat]`, droid_net.py:388-389) a
 GRU convolutions read channels [0,128) from the hidden state (or r*net) and [128,448) from one
 [E,h,w,320] buffer that the encoders write into.
 
-13 launches per update, all hand-written MFMA implicit-GEMM convolutions (csrc/conv_mfma.hip) with fused
+A dozen launches per update, all hand-written MFMA implicit-GEMM convolutions (csrc/conv_mfma.hip) with fused
 epilogues:
     corr0 (1x1 200->128, relu) -> corr2 (3x3, relu)            -> xbuf[128:256]
     flow0 (7x7 4->128, relu)   -> flow2 (3x3 128->64, relu)    -> xbuf[256:320]
     w     (1x1, sigmoid * net, summed over pixels)             -> glo_sum        [GLO epilogue]
     convz|convr (3x3 448->256): z, r*net                                          [ZR epilogue]
     convq (3x3 448->128): net' = (1-z) net + z tanh(.)                            [Q epilogue]
-    delta0|weight0|agg1 (3x3 128->384, relu) -> delta2|weight2 (3x3 256->4)       [HEADS epilogue]
-    agg2 (3x3, relu) -> eta (3x3 128->1, 0.01 softplus)                           [ETA epilogue]
+    agg1 (3x3 128->128, relu) -> hbuf[256:384] -> segmented mean -> agg2 (3x3, relu) -> eta (3x3 128->1, 0.01 softplus)
+                                                                                  [ETA epilogue]
+    delta0|weight0 (3x3 128->256, relu) -> hbuf[0:256] -> delta2|weight2 (3x3 256->4)  [HEADS epilogue]
+      on grids of 4 x 64 tiles: delta2|weight2 contracted in delta0|weight0's epilogue + a finish pass, no hbuf[0:256]
 
 There is no other backend: the torch / MIOpen formulation used as the A/B baseline of these kernels lives in
 scratch/miopen_ab.py (diagnostic, not importable from the package).
@@ -32,7 +34,7 @@ UpdateBuffers = parse_struct("vipe_update_buffers")
 GateStateJob = parse_struct("vipe_gate_state_job")
 
 ACT = {"none": 0, "relu": 1, "sigmoid": 2, "tanh": 3}
-EPI = {"plain": 0, "glo": 1, "zr": 2, "q": 3, "heads": 4, "eta": 5, "partial": 6}
+EPI = {"plain": 0, "glo": 1, "zr": 2, "q": 3, "heads": 4, "eta": 5, "partial": 6, "heads_fused": 7}
 ACCINIT_F32 = 0x100  # VIPE_CONV_ACCINIT_F32
 CORR_CH = 200  # 196 correlation channels padded to a multiple of 8 (zeros)
 
@@ -55,6 +57,28 @@ class _Packed:
         self.bias = torch.zeros(cp.value, dtype=torch.float32, device=device)
         self.bias[:self.cout] = bias.detach().to(device=device, dtype=torch.float32).reshape(-1)
         self.flops_per_pixel = 2.0 * self.cout * self.cin * self.kh * self.kw
+
+
+def heads2_fragment_index():
+    """Where each element of the fused heads' A operand comes from (include/vipe_amd.h, vipe_conv2d_fused mode 7):
+    int64 arrays (out, channel, tap, valid) of shape [2, 2, 2, 2, 64, 8] = [cout slice s][cout half h][row block rb]
+    [cout-block pair ip][lane][e].  Row 16 rb + lane % 16 of the A matrix is (tap, o) = divmod(row, 2), zero from row
+    18 on; the lane's 8 k-values are the channels its accumulators hold of the cout blocks 2 ip and 2 ip + 1
+    (4 consecutive ones each, starting at 4 (lane / 16)): the B operand is built from the accumulators in place."""
+    import numpy as np
+    s, h, rb, ip, lane, e = np.meshgrid(*[np.arange(n) for n in (2, 2, 2, 2, 64, 8)], indexing="ij")
+    row = 16 * rb + lane % 16
+    tap, o = row // 2, row % 2
+    ch = 128 * s + 64 * h + 16 * (2 * ip + e // 4) + 4 * (lane // 16) + e % 4
+    valid = row < 18
+    return np.where(valid, 2 * s + o, 0), ch, np.where(valid, tap, 0), valid
+
+
+def pack_heads2_fragments(h2_oihw):
+    """[4,256,3,3] block-diagonal heads2 weights -> the flat fp16 fragment tensor of `heads2_fragment_index`"""
+    out, ch, tap, valid = (torch.from_numpy(a).to(h2_oihw.device) for a in heads2_fragment_index())
+    w = h2_oihw.reshape(4, 256, 9)[out, ch, tap]
+    return torch.where(valid, w, torch.zeros_like(w)).to(torch.float16).contiguous().reshape(-1)
 
 
 def segment_csr(ix, n_src):
@@ -114,12 +138,20 @@ class UpdateEngine:
         ww0, bw0 = wb(m.weight[0])
         wa1, ba1 = wb(m.agg.conv1)
         self.heads0 = _Packed(torch.cat([wd0, ww0, wa1], 0), torch.cat([bd0, bw0, ba1], 0), d)
+        # the same convolution packed by consumer: GraphAgg's input (hbuf[..., 256:]) first, so that its chain starts
+        # beside the flow / weight heads' 256 channels instead of behind all 384 (VIPE_AMD_HEADS_BY_CONSUMER=0: one launch)
+        self.heads_by_consumer = os.environ.get("VIPE_AMD_HEADS_BY_CONSUMER", "1") != "0"
+        self.agg1 = _Packed(wa1, ba1, d)
+        self.heads_dw = _Packed(torch.cat([wd0, ww0], 0), torch.cat([bd0, bw0], 0), d)
         wd2, bd2 = wb(m.delta[2])
         ww2, bw2 = wb(m.weight[2])
         h2 = torch.zeros(4, 256, 3, 3, device=d, dtype=f16)
         h2[0:2, 0:128] = wd2[:2]
         h2[2:4, 128:256] = ww2[:2]
         self.heads2 = _Packed(h2, torch.cat([bd2[:2], bw2[:2]], 0), d)
+        self.heads2_frag = pack_heads2_fragments(h2)  # for the heads contracted in heads_dw's epilogue (4 x 64 tiles)
+        # the library reads the same switch (vipe_heads_fused_ok); an engine built with it off hands over no fragments
+        self.fused_heads_on = self.heads_by_consumer and os.environ.get("VIPE_AMD_FUSED_HEADS", "1") != "0"
         self.agg2 = _Packed(*wb(m.agg.conv2), d)
         self.eta = _Packed(*wb(m.agg.eta[0]), d)
         self.upmask = _Packed(*wb(m.agg.upmask[0]), d)
@@ -137,6 +169,11 @@ class UpdateEngine:
         wd_.zr_s_w, wd_.q_s_w = self.zr_s.packed.data_ptr(), self.q_s.packed.data_ptr()
         wd_.zr_n_w, wd_.zr_x_w = self.zr_n.packed.data_ptr(), self.zr_x.packed.data_ptr()
         wd_.glo_wT, wd_.glo_b = self.glo_w.data_ptr(), self.glo_b.data_ptr()
+        if self.heads_by_consumer:
+            wd_.agg1_w, wd_.agg1_b = self.agg1.packed.data_ptr(), self.agg1.bias.data_ptr()
+            wd_.heads_dw_w, wd_.heads_dw_b = self.heads_dw.packed.data_ptr(), self.heads_dw.bias.data_ptr()
+            if self.fused_heads_on:
+                wd_.heads2_frag = self.heads2_frag.data_ptr()
         self._wdesc = wd_
         self._bdesc = {}
 
@@ -244,6 +281,16 @@ class UpdateEngine:
         return (gs is not None and pgate is not None and gs["net_ptr"] == net.data_ptr() and
                 gs["pgate_ptr"] == pgate.data_ptr() and gs["shape"] == tuple(net.shape) and gs.get("gen") == self._gate_gen)
 
+    def fused_heads(self, H, W):
+        """the library's own predicate (vipe_heads_fused_ok: 4 x 64 tiles, VIPE_AMD_FUSED_HEADS) for the heads contracted
+        in their producer's epilogue; needs the heads packed by consumer"""
+        return self.fused_heads_on and bool(lib().vipe_heads_fused_ok(H, W))
+
+    def _hborder(self, E, H, W):
+        n = ctypes.c_int64()
+        check(lib().vipe_heads_border_floats(E, H, W, ctypes.addressof(n)), "heads_border_floats")
+        return self._buf("hborder", (n.value,), torch.float32)
+
     def _buf(self, name, shape, dtype=torch.float16):
         t = self._bufs.get(name)
         if t is None or tuple(t.shape) != tuple(shape) or t.dtype != dtype:
@@ -320,18 +367,17 @@ class UpdateEngine:
             self._conv(self.zr, net, 0, E, H, W, x1=xbuf, split=128, y=zb, y2=rnet, net=net, mode="zr", extra=extra)
             self._conv(self.q, rnet, 0, E, H, W, x1=xbuf, split=128, y=net_out, net=net, z=zb, mode="q", extra=extra,
                        extra_off=256)
-        # heads + first aggregation conv on net' (droid_net.py:486-487, 418)
-        self._conv(self.heads0, net_out, 0, E, H, W, y=hbuf, act="relu")
-        self._conv(self.heads2, hbuf, 0, E, H, W, mode="heads", fout=dw, cin=256)
-        eta = upmask = None
-        if ix is not None:
-            if n_src is None:  # the reference syncs here too (scatter.py:40: int(index.max()) + 1)
-                n_src = int(ix.max().item()) + 1 if ix.numel() else 0
+        # heads + first aggregation conv on net' (droid_net.py:486-487, 418), in vipe_update_operator's order: in its
+        # two-stream form GraphAgg's 128 channels and its chain first, then the heads (fused on 4 x 64 tiles); otherwise
+        # the one 384-channel launch, the heads, the chain
+        if n_src is None and ix is not None:  # the reference syncs here too (scatter.py:40: int(index.max()) + 1)
+            n_src = int(ix.max().item()) + 1 if ix.numel() else 0
+        eta = upmask = a2 = None
+
+        def agg_chain():
             # scatter_mean over the edges of each source node (droid_net.py:420-421): deterministic segmented mean
-            # over a CSR of the edges (built once per edge set by the caller, or here)
-            if csr is None:
-                csr = segment_csr(ix, n_src)
-            order, rowptr = csr
+            # over a CSR of the edges (built once per edge set by the caller, or here), agg conv 2, eta (:422-429)
+            order, rowptr = csr if csr is not None else segment_csr(ix, n_src)
             agg = self._buf("agg", (n_src, H, W, 128))
             check(lib().vipe_segment_mean_nhwc_f16(ptr(hbuf), 384, 256, ptr(order), ptr(rowptr), ptr(agg), n_src, H * W,
                                                    128, stream_ptr(hbuf)), "segment_mean")
@@ -339,9 +385,29 @@ class UpdateEngine:
             eta = self._buf("eta", (n_src, H, W), torch.float32)
             self._conv(self.agg2, agg, 0, n_src, H, W, y=a2, act="relu")
             self._conv(self.eta, a2, 0, n_src, H, W, mode="eta", fout=eta)
-            if want_upmask:
-                upmask = torch.empty((n_src, H, W, 576), dtype=torch.float16, device=self.device)
-                self._conv(self.upmask, a2, 0, n_src, H, W, y=upmask)
+            return a2, eta
+
+        chain = ix is not None and n_src > 0
+        if self.heads_by_consumer and chain and E >= self.op_side_min_edges:  # the native call's two-stream form
+            self._conv(self.agg1, net_out, 0, E, H, W, y=hbuf, y_coff=256, act="relu")
+            a2, eta = agg_chain()
+            if self.fused_heads(H, W):
+                hborder = self._hborder(E, H, W)
+                self._conv(self.heads_dw, net_out, 0, E, H, W, act="relu", mode="heads_fused", net=self.heads2_frag,
+                           y2=hborder, fout=dw)
+                check(lib().vipe_heads_finish(ptr(dw), ptr(hborder), ptr(self.heads2.bias), E, H, W, stream_ptr(dw)),
+                      "heads_finish")
+            else:
+                self._conv(self.heads_dw, net_out, 0, E, H, W, y=hbuf, act="relu")
+                self._conv(self.heads2, hbuf, 0, E, H, W, mode="heads", fout=dw, cin=256)
+        else:
+            self._conv(self.heads0, net_out, 0, E, H, W, y=hbuf, act="relu")
+            self._conv(self.heads2, hbuf, 0, E, H, W, mode="heads", fout=dw, cin=256)
+            if ix is not None:
+                a2, eta = agg_chain()
+        if ix is not None and want_upmask:
+            upmask = torch.empty((n_src, H, W, 576), dtype=torch.float16, device=self.device)
+            self._conv(self.upmask, a2, 0, n_src, H, W, y=upmask)
         return net_out, dw, eta, upmask
 
     def _forward_native(self, net, xbuf, corr, motn, ix, n_src, net_out, want_upmask, csr, pgate, scratch,
@@ -360,7 +426,9 @@ class UpdateEngine:
             a2 = self._buf("a2", (n_src, H, W, 128))
             eta = self._buf("eta", (n_src, H, W), torch.float32)  # persistent: callers consume it before the next call
         lookup = isinstance(corr, tuple)
-        tensors = (net, net_out, xbuf, motn, pgate, c1, f1, zb, rnet, hbuf, dw, glo, extra, order, rowptr, agg, a2, eta) + \
+        hborder = self._hborder(E, H, W) if self.fused_heads(H, W) else None
+        tensors = (net, net_out, xbuf, motn, pgate, c1, f1, zb, rnet, hbuf, dw, glo, extra, order, rowptr, agg, a2, eta,
+                   hborder) + \
             ((tuple(corr[1]) + (corr[2],) + ((corr[3],) if len(corr) > 3 and corr[3] is not None else ())) if lookup else (corr,))
         pzr = gate_state["pzr"] if gate_state is not None else None
         two_streams = E >= self.op_side_min_edges
@@ -390,7 +458,7 @@ class UpdateEngine:
                 b.corr = corr.data_ptr()
             for name, t in dict(motn=motn, net=net, net_out=net_out, xbuf=xbuf, pgate=pgate, c1=c1, f1=f1, zb=zb, rnet=rnet,
                                 hbuf=hbuf, dw=dw, glo=glo, extra=extra, order=order, rowptr=rowptr, agg=agg, a2=a2,
-                                eta=eta).items():
+                                eta=eta, hborder=hborder).items():
                 setattr(b, name, None if t is None else t.data_ptr())
             if pzr is not None:
                 b.pzr, b.gate_state = pzr.data_ptr(), int(gate_state["n_staged"])
