@@ -515,7 +515,9 @@ int vipe_conv_packed_dims(int Cout, int Cin, int KH, int KW, int* cout_pad, int*
  *             iteration on a side stream while the dense BA of the current one leaves the chip idle.
  *   7 HEADS_FUSED  Cin = 128, Cout = 256, 3x3, relu, H % 4 == 0 and W % 64 == 0 (VIPE_EUNSUPPORTED otherwise): the
  *             convolution delta0 | weight0 with the 3x3 flow / weight heads (mode 4 over its output) contracted in its
- *             epilogue - nothing of the 256 channels is stored.  d_net = the heads2 weights as matrix fragments
+ *             epilogue - nothing of the 256 channels is stored.  This mode has no hidden state and no second output, and
+ *             its two operands travel in their slots - a matter of this positional ABI alone; inside the library they
+ *             have names of their own (csrc/conv_call.cuh).  d_net = the heads2 weights as matrix fragments
  *             (fp16 [cout slice s = 2][cout half h = 2][row block rb = 2][ip = 2][lane = 64][e = 8]: the weight
  *             of output 2 s + o, tap t, with 2 t + o = 16 rb + lane % 16 (zero from 18 on), for input channel
  *             128 s + 64 h + 32 ip + 16 (e / 4) + 4 (lane / 16) + e % 4), d_fout = [B*H*W, 4] f32 and
@@ -530,8 +532,9 @@ int vipe_conv_packed_dims(int Cout, int Cin, int KH, int KW, int* cout_pad, int*
 #define VIPE_CONV_ACCINIT_F32 0x100
 /* d_accinit (optional, fp16 [B*H*W, ai_ctot], channels [ai_coff, ai_coff + Cout)): initial value of the accumulators,
  * i.e. a precomputed partial sum over OTHER input channels (convolution is linear in its input channels).  Used to
- * hoist the context-feature part of the GRU gates, constant per edge, out of the update iteration.  Supported for
- * image widths that are multiples of 64 and Cout >= 64; VIPE_EUNSUPPORTED otherwise. */
+ * hoist the context-feature part of the GRU gates, constant per edge, out of the update iteration.  Taken by the tile
+ * kernels only: 1x1 / 3x3 with Cout >= 64 on grids made of 4 x 64 tiles (H % 4 == 0 and W % 64 == 0) or, for every other
+ * grid, the flat tiling up to 126 columns; VIPE_EUNSUPPORTED otherwise. */
 int vipe_conv2d_fused(const void* d_x0, int x0_ctot, int x0_coff, const void* d_x1, int x1_ctot, int x1_coff,
                       int split, const void* d_w_packed, const float* d_bias, const float* d_extra, int extra_stride,
                       int extra_off, void* d_y, int y_ctot, int y_coff, void* d_y2, int y2_ctot, int y2_coff,

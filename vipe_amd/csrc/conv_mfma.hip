@@ -22,6 +22,7 @@
 #include <type_traits>
 
 #include "common.cuh"
+#include "conv_call.cuh"
 
 namespace {
 
@@ -29,8 +30,6 @@ typedef _Float16 half8 __attribute__((ext_vector_type(8)));
 typedef _Float16 half4 __attribute__((ext_vector_type(4)));
 typedef float float16v __attribute__((ext_vector_type(16)));
 typedef float float4v __attribute__((ext_vector_type(4)));
-
-enum Epi { EPI_PLAIN = 0, EPI_GLO = 1, EPI_ZR = 2, EPI_Q = 3, EPI_HEADS = 4, EPI_ETA = 5, EPI_PARTIAL = 6, EPI_HEADS_FUSED = 7 };
 
 struct ConvArgs {
   const half_t* x0; int x0_ctot, x0_coff;  // input channels [0, split)
@@ -1404,7 +1403,7 @@ int launch_halo_family(ConvArgs& a, int cp, int64_t M, hipStream_t s) {
   const int tiles = FLAT ? a.B * a.f_tiles : (int)(M / (HALO_TH * HALO_TW));
   const size_t xb = FLAT ? (size_t)a.f_xbytes : (size_t)H32_XBYTES;
   if (a.epi == EPI_HEADS_FUSED) {
-    // the aligned 128 -> 256 3x3 with the heads contracted in its epilogue (validated by vipe_conv2d_fused)
+    // the aligned 128 -> 256 3x3 with the heads contracted in its epilogue (validated by vipe_conv_run)
     if constexpr (FLAT) return VIPE_EUNSUPPORTED;
     else return launch_halo32<128, 3, 3, false>(a, tiles, 2, 3 * (size_t)128 * 64 + 2 * xb + 1024, s);
   }
@@ -1444,6 +1443,19 @@ int launch_halo_family(ConvArgs& a, int cp, int64_t M, hipStream_t s) {
   return launch_halo32<32, 1, 0, FLAT>(a, tiles, 1, lds, s);
 }
 
+// the per-tap gather kernels of one channel tile, any shape: register staging for Cin = 4 (128-channel tiles only) and
+// for more than 32 taps, LDS-DMA otherwise
+template <int BMC, int WM, int WN>
+int launch_gather(const ConvArgs& a, bool small, bool glds, int gx, int gy, hipStream_t s) {
+  const size_t lds = 2 * (BMC + BNP) * 128;
+  if (small) {
+    if constexpr (BMC != 128) return VIPE_EUNSUPPORTED;
+    else conv_mfma_kernel<BMC, WM, WN, true><<<dim3(gx, gy), 256, lds, s>>>(a);
+  } else if (glds) conv_mfma_glds_kernel<BMC, WM, WN><<<dim3(gx * gy), 256, lds, s>>>(a, gy);
+  else conv_mfma_kernel<BMC, WM, WN, false><<<dim3(gx, gy), 256, lds, s>>>(a);
+  return vipe_launch_status();
+}
+
 // Dispatch, in this order:
 //  1. a call that needs a tile kernel on a grid no tile kernel takes: VIPE_EUNSUPPORTED;
 //  2. GLO, 128 -> 128 1x1 with `net` as its own input: conv1x1_glo_kernel (any grid);
@@ -1480,15 +1492,11 @@ int launch_conv(ConvArgs& a, hipStream_t s) {
     conv1x1_glo_kernel<<<dim3((unsigned)(a.B * ((a.H * a.W + 255) / 256))), 512, GLO_LDS, s>>>(a);
     return vipe_launch_status();
   }
-  if (halo) {
-    const int rc = launch_halo_family<false>(a, cp, M, s);
-    if (rc != VIPE_EUNSUPPORTED || needs_tile_kernel(a)) return rc;
-  } else if (flat) {
-    const int rc = launch_halo_family<true>(a, cp, M, s);
+  if (halo || flat) {
+    const int rc = halo ? launch_halo_family<false>(a, cp, M, s) : launch_halo_family<true>(a, cp, M, s);
     if (rc != VIPE_EUNSUPPORTED || needs_tile_kernel(a)) return rc;
   }
-  if (small && a.KH == 7 && a.KW == 7 && cp % 128 == 0 && kp == 256 && a.epi == EPI_PLAIN && a.extra == nullptr &&
-      (int64_t)a.B * a.H * a.W < (1ll << 31)) {
+  if (small && a.KH == 7 && a.KW == 7 && cp % 128 == 0 && kp == 256 && a.epi == EPI_PLAIN && !a.extra && off32) {
     const int gy = cp / 128;
     if (aligned) {
       static std::atomic<uint64_t> seen{0};
@@ -1506,57 +1514,76 @@ int launch_conv(ConvArgs& a, hipStream_t s) {
       return vipe_launch_status();
     }
   }
-  // per-tap gather kernels: any shape
   const bool glds = !small && a.KH * a.KW <= 32;
   static std::atomic<uint64_t> s1{0}, s2{0}, s3{0};
   allow_lds(conv_mfma_kernel<128, 2, 2, false>, s1, 65536);
   allow_lds(conv_mfma_kernel<128, 2, 2, true>, s2, 65536);
   allow_lds(conv_mfma_glds_kernel<128, 2, 2>, s3, 65536);
-  if (cp >= 128) {
-    const size_t lds = 2 * (128 + BNP) * 128;
-    const int gy = cp / 128;
-    if (small) conv_mfma_kernel<128, 2, 2, true><<<dim3(gx, gy), 256, lds, s>>>(a);
-    else if (glds) conv_mfma_glds_kernel<128, 2, 2><<<dim3(gx * gy), 256, lds, s>>>(a, gy);
-    else conv_mfma_kernel<128, 2, 2, false><<<dim3(gx, gy), 256, lds, s>>>(a);
-  } else if (cp == 64) {
-    const size_t lds = 2 * (64 + BNP) * 128;
-    if (small) return VIPE_EUNSUPPORTED;
-    if (glds) conv_mfma_glds_kernel<64, 1, 4><<<dim3(gx), 256, lds, s>>>(a, 1);
-    else conv_mfma_kernel<64, 1, 4, false><<<dim3(gx, 1), 256, lds, s>>>(a);
-  } else {
-    const size_t lds = 2 * (32 + BNP) * 128;
-    if (small) return VIPE_EUNSUPPORTED;
-    if (glds) conv_mfma_glds_kernel<32, 1, 4><<<dim3(gx), 256, lds, s>>>(a, 1);
-    else conv_mfma_kernel<32, 1, 4, false><<<dim3(gx, 1), 256, lds, s>>>(a);
-  }
-  return vipe_launch_status();
+  if (cp >= 128) return launch_gather<128, 2, 2>(a, small, glds, gx, cp / 128, s);
+  if (cp == 64) return launch_gather<64, 1, 4>(a, small, glds, gx, 1, s);
+  return launch_gather<32, 1, 4>(a, small, glds, gx, 1, s);
 }
 
 }  // namespace
 
+// the one route to the kernels above: all argument validation, then the kernels' argument block
+int vipe_conv_run(const ConvCall& c, hipStream_t stream) {
+  const int Cin = c.Cin, Cout = c.Cout;
+  VIPE_CHECK_ARG(c.x0.p && c.w && c.bias);
+  VIPE_CHECK_ARG(!c.accinit.p || (c.accinit.ctot % 4 == 0 && c.accinit.coff % 4 == 0 && c.accinit.coff + Cout <= c.accinit.ctot));
+  VIPE_CHECK_ARG(c.B >= 0 && c.H > 0 && c.W > 0 && Cin > 0 && Cout > 0 && (c.KH & 1) && (c.KW & 1));
+  if (Cin == 4) {
+    VIPE_CHECK_ARG(c.split >= Cin && c.x0.ctot % 4 == 0 && c.x0.coff % 4 == 0);
+  } else {
+    VIPE_CHECK_ARG(Cin % 8 == 0 && c.x0.ctot % 8 == 0 && c.x0.coff % 8 == 0);
+    VIPE_CHECK_ARG(c.split >= Cin || (c.split % 64 == 0 && c.x1.p && c.x1.ctot % 8 == 0 && c.x1.coff % 8 == 0));
+  }
+  VIPE_CHECK_ARG(c.epi >= EPI_PLAIN && c.epi <= EPI_HEADS_FUSED);
+  if (c.epi == EPI_HEADS_FUSED) {
+    VIPE_CHECK_ARG(c.fout && c.heads2_frag && c.border && Cin == 128 && Cout == 256 && c.KH == 3 && c.KW == 3 &&
+                   c.act == VIPE_ACT_RELU && !c.extra && !c.accinit.p && !c.accinit_f32 && c.split >= Cin);
+    if (c.H % HALO_TH != 0 || c.W % HALO_TW != 0) return VIPE_EUNSUPPORTED;
+  }
+  if (c.epi == EPI_PARTIAL) VIPE_CHECK_ARG(c.fout && c.y.ctot % 4 == 0 && c.y.coff % 4 == 0 && c.y.coff + Cout <= c.y.ctot && !c.extra);
+  if (c.epi == EPI_PLAIN) VIPE_CHECK_ARG(c.y.p && c.y.ctot % 4 == 0 && c.y.coff % 4 == 0);
+  if (c.epi == EPI_GLO) VIPE_CHECK_ARG(c.net.p && c.fout);
+  if (c.epi == EPI_ZR) VIPE_CHECK_ARG(c.y.p && c.y2.p && c.net.p && Cout == 256);
+  if (c.epi == EPI_Q) VIPE_CHECK_ARG(c.y.p && c.net.p && c.z && Cout == 128);
+  if (c.epi == EPI_HEADS) VIPE_CHECK_ARG(c.fout && Cout == 4);
+  if (c.epi == EPI_ETA) VIPE_CHECK_ARG(c.fout && Cout == 1);
+  const ConvView& x1 = c.x1.p ? c.x1 : c.x0;
+  ConvArgs a = {};
+  a.x0 = (const half_t*)c.x0.p; a.x0_ctot = c.x0.ctot; a.x0_coff = c.x0.coff;
+  a.x1 = (const half_t*)x1.p; a.x1_ctot = x1.ctot; a.x1_coff = x1.coff;
+  a.split = c.split > Cin ? Cin : c.split;
+  a.w = (const half_t*)c.w; a.bias = c.bias; a.extra = c.extra; a.extra_stride = c.extra_stride; a.extra_off = c.extra_off;
+  a.y = (half_t*)c.y.p; a.y_ctot = c.y.ctot; a.y_coff = c.y.coff;
+  a.y2 = (half_t*)c.y2.p; a.y2_ctot = c.y2.ctot; a.y2_coff = c.y2.coff;
+  a.w2 = (const half_t*)c.heads2_frag; a.border = c.border;
+  a.net = (const half_t*)c.net.p; a.net_ctot = c.net.ctot; a.net_coff = c.net.coff;
+  a.zbuf = (const half_t*)c.z; a.fout = c.fout;
+  a.accinit = (const half_t*)c.accinit.p; a.ai_ctot = c.accinit.ctot; a.ai_coff = c.accinit.coff; a.ai_f32 = c.accinit_f32;
+  a.B = c.B; a.H = c.H; a.W = c.W; a.Cin = Cin; a.Cout = Cout; a.KH = c.KH; a.KW = c.KW;
+  a.act = c.act; a.epi = c.epi;
+  return launch_conv(a, stream);
+}
+
 extern "C" {
 
+// The two positional entry points are translations into a ConvCall and nothing else.
 VIPE_EXPORT int vipe_conv2d_nhwc_f16(const void* d_x, const void* d_w_packed, const float* d_bias,
                                      const float* d_extra, void* d_y, int B, int H, int W, int Cin, int cin_total,
                                      int cin_off, int Cout, int cout_total, int cout_off, int KH, int KW, int act,
                                      void* stream) {
-  VIPE_CHECK_ARG(d_x && d_w_packed && d_bias && d_y);
-  VIPE_CHECK_ARG(B >= 0 && H > 0 && W > 0 && Cin > 0 && Cout > 0 && (KH & 1) && (KW & 1));
-  VIPE_CHECK_ARG((Cin == 4 || Cin % 8 == 0) && cin_total % 4 == 0 && cin_off % 4 == 0 && cout_total % 4 == 0 &&
-                 cout_off % 4 == 0);
-  VIPE_CHECK_ARG(Cin == 4 || (cin_total % 8 == 0 && cin_off % 8 == 0));
-  VIPE_CHECK_ARG(act >= 0 && act <= 3);
-  ConvArgs a = {};
-  a.x0 = (const half_t*)d_x; a.x0_ctot = cin_total; a.x0_coff = cin_off;
-  a.x1 = a.x0; a.x1_ctot = cin_total; a.x1_coff = cin_off; a.split = Cin;
-  a.w = (const half_t*)d_w_packed; a.bias = d_bias; a.extra = d_extra; a.extra_stride = Cout; a.extra_off = 0;
-  a.y = (half_t*)d_y; a.y_ctot = cout_total; a.y_coff = cout_off;
-  a.B = B; a.H = H; a.W = W; a.Cin = Cin; a.Cout = Cout; a.KH = KH; a.KW = KW;
-  a.act = act; a.epi = EPI_PLAIN;
-  return launch_conv(a, as_stream(stream));
+  VIPE_CHECK_ARG(act >= 0 && act <= 3);  // of this entry point alone: vipe_conv2d_fused takes any other value as "none"
+  ConvCall c;
+  c.x0 = {d_x, cin_total, cin_off}; c.y = {d_y, cout_total, cout_off};
+  c.w = d_w_packed; c.bias = d_bias; c.extra = d_extra; c.extra_stride = Cout;
+  c.B = B; c.H = H; c.W = W; c.Cin = Cin; c.Cout = Cout; c.KH = KH; c.KW = KW; c.act = act;
+  return vipe_conv_run(c, as_stream(stream));
 }
 
-// [fused] GRU / head epilogues.  `mode`: 1 GLO, 2 ZR, 3 Q, 4 HEADS, 5 ETA (see conv_mfma.hip); two-source input.
+// [fused] GRU / head epilogues.  `mode`: 1 GLO, 2 ZR, 3 Q, 4 HEADS, 5 ETA, 6 PARTIAL, 7 HEADS_FUSED; two-source input.
 VIPE_EXPORT int vipe_conv2d_fused(const void* d_x0, int x0_ctot, int x0_coff, const void* d_x1, int x1_ctot,
                                   int x1_coff, int split, const void* d_w_packed, const float* d_bias,
                                   const float* d_extra, int extra_stride, int extra_off, void* d_y, int y_ctot,
@@ -1564,47 +1591,20 @@ VIPE_EXPORT int vipe_conv2d_fused(const void* d_x0, int x0_ctot, int x0_coff, co
                                   int net_coff, const void* d_z, float* d_fout, const void* d_accinit, int ai_ctot,
                                   int ai_coff, int B, int H, int W, int Cin, int Cout, int KH, int KW, int act, int mode,
                                   void* stream) {
-  VIPE_CHECK_ARG(d_x0 && d_w_packed && d_bias);
-  VIPE_CHECK_ARG(!d_accinit || (ai_ctot % 4 == 0 && ai_coff % 4 == 0 && ai_coff + Cout <= ai_ctot));
-  VIPE_CHECK_ARG(B >= 0 && H > 0 && W > 0 && Cin > 0 && Cout > 0 && (KH & 1) && (KW & 1));
-  if (Cin == 4) {
-    VIPE_CHECK_ARG(split >= Cin && x0_ctot % 4 == 0 && x0_coff % 4 == 0);
-  } else {
-    VIPE_CHECK_ARG(Cin % 8 == 0 && x0_ctot % 8 == 0 && x0_coff % 8 == 0);
-    VIPE_CHECK_ARG(split >= Cin || (split % 64 == 0 && d_x1 && x1_ctot % 8 == 0 && x1_coff % 8 == 0));
+  ConvCall c;
+  c.x0 = {d_x0, x0_ctot, x0_coff}; c.x1 = {d_x1, x1_ctot, x1_coff}; c.split = split;
+  c.w = d_w_packed; c.bias = d_bias; c.extra = d_extra; c.extra_stride = extra_stride; c.extra_off = extra_off;
+  c.y = {d_y, y_ctot, y_coff}; c.y2 = {d_y2, y2_ctot, y2_coff}; c.net = {d_net, net_ctot, net_coff};
+  c.z = d_z; c.fout = d_fout;
+  c.accinit = {d_accinit, ai_ctot, ai_coff}; c.accinit_f32 = (mode & VIPE_CONV_ACCINIT_F32) != 0;
+  c.B = B; c.H = H; c.W = W; c.Cin = Cin; c.Cout = Cout; c.KH = KH; c.KW = KW;
+  c.act = act; c.epi = mode & ~VIPE_CONV_ACCINIT_F32;
+  if (c.epi == EPI_HEADS_FUSED) {
+    // a matter of this ABI alone: mode 7 has no slots of its own, its fragments travel as d_net and its border sums as d_y2
+    c.heads2_frag = d_net; c.border = (float*)d_y2;
+    c.net.p = c.y2.p = nullptr;
   }
-  const int ai_f32 = (mode & VIPE_CONV_ACCINIT_F32) != 0;
-  mode &= ~VIPE_CONV_ACCINIT_F32;
-  VIPE_CHECK_ARG(mode >= EPI_PLAIN && mode <= EPI_HEADS_FUSED);
-  if (mode == EPI_HEADS_FUSED) {
-    VIPE_CHECK_ARG(d_fout && d_net && d_y2 && Cin == 128 && Cout == 256 && KH == 3 && KW == 3 && act == VIPE_ACT_RELU &&
-                   !d_extra && !d_accinit && !ai_f32 && split >= Cin);
-    if (H % HALO_TH != 0 || W % HALO_TW != 0) return VIPE_EUNSUPPORTED;
-  }
-  if (mode == EPI_PARTIAL) VIPE_CHECK_ARG(d_fout && y_ctot % 4 == 0 && y_coff % 4 == 0 && y_coff + Cout <= y_ctot && !d_extra);
-  if (mode == EPI_PLAIN) VIPE_CHECK_ARG(d_y && y_ctot % 4 == 0 && y_coff % 4 == 0);
-  if (mode == EPI_GLO) VIPE_CHECK_ARG(d_net && d_fout);
-  if (mode == EPI_ZR) VIPE_CHECK_ARG(d_y && d_y2 && d_net && Cout == 256);
-  if (mode == EPI_Q) VIPE_CHECK_ARG(d_y && d_net && d_z && Cout == 128);
-  if (mode == EPI_HEADS) VIPE_CHECK_ARG(d_fout && Cout == 4);
-  if (mode == EPI_ETA) VIPE_CHECK_ARG(d_fout && Cout == 1);
-  ConvArgs a = {};
-  a.x0 = (const half_t*)d_x0; a.x0_ctot = x0_ctot; a.x0_coff = x0_coff;
-  a.x1 = (const half_t*)(d_x1 ? d_x1 : d_x0); a.x1_ctot = d_x1 ? x1_ctot : x0_ctot; a.x1_coff = d_x1 ? x1_coff : x0_coff;
-  a.split = split > Cin ? Cin : split;
-  a.w = (const half_t*)d_w_packed; a.bias = d_bias; a.extra = d_extra; a.extra_stride = extra_stride; a.extra_off = extra_off;
-  a.y = (half_t*)d_y; a.y_ctot = y_ctot; a.y_coff = y_coff;
-  a.y2 = (half_t*)d_y2; a.y2_ctot = y2_ctot; a.y2_coff = y2_coff;
-  if (mode == EPI_HEADS_FUSED) {
-    a.w2 = (const half_t*)d_net; a.border = (float*)d_y2;
-    d_net = nullptr; a.y2 = nullptr;
-  }
-  a.net = (const half_t*)d_net; a.net_ctot = net_ctot; a.net_coff = net_coff;
-  a.zbuf = (const half_t*)d_z; a.fout = d_fout;
-  a.accinit = (const half_t*)d_accinit; a.ai_ctot = ai_ctot; a.ai_coff = ai_coff; a.ai_f32 = ai_f32;
-  a.B = B; a.H = H; a.W = W; a.Cin = Cin; a.Cout = Cout; a.KH = KH; a.KW = KW;
-  a.act = act; a.epi = mode;
-  return launch_conv(a, as_stream(stream));
+  return vipe_conv_run(c, as_stream(stream));
 }
 
 VIPE_EXPORT int vipe_heads_fused_ok(int H, int W) {

@@ -180,9 +180,15 @@ class UpdateEngine:
     # ------------------------------------------------------------------ launches
     def _conv(self, pk, x0, x0_coff, B, H, W, y=None, y_coff=0, act="none", mode="plain", x1=None, x1_coff=0,
               split=None, extra=None, extra_off=0, y2=None, y2_coff=0, net=None, net_coff=0, z=None, fout=None,
-              cin=None, accinit=None, ai_coff=0):
+              cin=None, accinit=None, ai_coff=0, w2=None, border=None):
+        """One `vipe_conv2d_fused` launch on x0's stream.  `w2` / `border`: the heads2 fragments and the border sums of
+        mode "heads_fused" - the C entry point has no slots of their own for them, they travel as d_net / d_y2; this is
+        the one place on the Python side that knows."""
         cin = pk.cin if cin is None else cin
         split = cin if split is None else split
+        if mode == "heads_fused":
+            assert net is None and y2 is None and w2 is not None and border is not None
+            net, y2 = w2, border
         check(lib().vipe_conv2d_fused(
             ptr(x0), x0.shape[-1], x0_coff, ptr(x1), x1.shape[-1] if x1 is not None else 0, x1_coff, split,
             ptr(pk.packed), ptr(pk.bias), ptr(extra), extra.shape[-1] if extra is not None else 0, extra_off,
@@ -221,15 +227,9 @@ class UpdateEngine:
         fp32 summation order.  `FactorGraph.update` issues this for the NEW hidden state on a second stream right after
         the operator, so that it runs while the dense BA (one busy workgroup for most of its time) has the chip."""
         E, H, W, _ = net.shape
-        Es = E if n_staged is None else max(1, min(E, int(n_staged)))  # the z|r part is staged for the first Es edges
-        self._gate_gen += 1
-        glo = self._buf("glo", (E, 128), torch.float32)
-        extra = self._buf("extra", (E, 384), torch.float32)
-        pzr = self._buf("pzr", (Es, H, W, 256), torch.float32)
+        gs, b, glo = self._gate_state(net, pgate, n_staged)
+        Es, pzr, extra = gs["n_staged"], gs["pzr"], gs["extra"]
         if native:
-            b = UpdateBuffers()
-            b.H, b.W = H, W
-            b.pgate, b.pzr, b.glo, b.extra = pgate.data_ptr(), pzr.data_ptr(), glo.data_ptr(), extra.data_ptr()
             for part, n in ((1, E), (2, Es)):
                 if parts & part:
                     b.E = n
@@ -243,8 +243,23 @@ class UpdateEngine:
                                              stream_ptr(glo)), "glo_context")
             if parts & 2:
                 self._conv(self.zr_n, net, 0, Es, H, W, mode="partial", fout=pzr, accinit=pgate, ai_coff=0)
-        return dict(net_ptr=net.data_ptr(), pgate_ptr=pgate.data_ptr(), shape=tuple(net.shape), pzr=pzr, extra=extra,
-                    n_staged=Es, gen=self._gate_gen)
+        return gs
+
+    def _gate_state(self, net, pgate, n_staged):
+        """What `hidden_gate_state` and `gate_state_job` share: a new generation, the scratch buffers, their descriptor
+        (E = the staged edges) and the result dict, which keeps the descriptor alive -> (dict, descriptor, glo)"""
+        E, H, W, _ = net.shape
+        Es = E if n_staged is None else max(1, min(E, int(n_staged)))  # the z|r part is staged for the first Es edges
+        self._gate_gen += 1
+        glo = self._buf("glo", (E, 128), torch.float32)
+        extra = self._buf("extra", (E, 384), torch.float32)
+        pzr = self._buf("pzr", (Es, H, W, 256), torch.float32)
+        b = UpdateBuffers()
+        b.E, b.H, b.W = Es, H, W
+        b.pgate, b.pzr, b.glo, b.extra = pgate.data_ptr(), pzr.data_ptr(), glo.data_ptr(), extra.data_ptr()
+        gs = dict(net_ptr=net.data_ptr(), pgate_ptr=pgate.data_ptr(), shape=tuple(net.shape), pzr=pzr, extra=extra,
+                  n_staged=Es, keep=(b,), gen=self._gate_gen)
+        return gs, b, glo
 
     def gate_state_job(self, net, pgate, fractions=None, n_staged=None):
         """The z|r part of `hidden_gate_state(net, pgate)` (parts = 2), not launched: (gate_state dict, overlap triple) for
@@ -252,15 +267,8 @@ class UpdateEngine:
         pieces (`vipe_update_gate_state_piece`) on the given stream while the BA's solve kernels run; `fractions`:
         share of the edges per piece (default: even).  The dict is valid once that BA call has returned, the stream has
         been joined AND `hidden_gate_state(net, pgate, parts=1)` has run; it keeps the descriptors alive."""
-        E_all, H, W, _ = net.shape
-        E = E_all if n_staged is None else max(1, min(E_all, int(n_staged)))  # the job covers the first E edges
-        self._gate_gen += 1
-        glo = self._buf("glo", (E_all, 128), torch.float32)
-        extra = self._buf("extra", (E_all, 384), torch.float32)
-        pzr = self._buf("pzr", (E, H, W, 256), torch.float32)
-        b = UpdateBuffers()
-        b.E, b.H, b.W = E, H, W
-        b.pgate, b.pzr, b.glo, b.extra = pgate.data_ptr(), pzr.data_ptr(), glo.data_ptr(), extra.data_ptr()
+        gs, b, _ = self._gate_state(net, pgate, n_staged)
+        E = gs["n_staged"]  # the job covers the first E edges
         job = GateStateJob()
         job.weights, job.buffers, job.net = ctypes.addressof(self._wdesc), ctypes.addressof(b), net.data_ptr()
         bounds = None
@@ -273,8 +281,7 @@ class UpdateEngine:
             bounds = (ctypes.c_int * len(cum))(*cum)
             job.bounds, job.n_bounds = ctypes.addressof(bounds), len(cum)
         fn = ctypes.cast(lib().vipe_update_gate_state_piece, ctypes.c_void_p).value
-        gs = dict(net_ptr=net.data_ptr(), pgate_ptr=pgate.data_ptr(), shape=tuple(net.shape), pzr=pzr, extra=extra,
-                  n_staged=E, keep=(b, job, bounds), gen=self._gate_gen)
+        gs["keep"] = (b, job, bounds)
         return gs, (lambda stream: (stream.cuda_stream, fn, ctypes.addressof(job)))
 
     def gate_state_matches(self, gs, net, pgate):
@@ -393,8 +400,8 @@ class UpdateEngine:
             a2, eta = agg_chain()
             if self.fused_heads(H, W):
                 hborder = self._hborder(E, H, W)
-                self._conv(self.heads_dw, net_out, 0, E, H, W, act="relu", mode="heads_fused", net=self.heads2_frag,
-                           y2=hborder, fout=dw)
+                self._conv(self.heads_dw, net_out, 0, E, H, W, act="relu", mode="heads_fused", w2=self.heads2_frag,
+                           border=hborder, fout=dw)
                 check(lib().vipe_heads_finish(ptr(dw), ptr(hborder), ptr(self.heads2.bias), E, H, W, stream_ptr(dw)),
                       "heads_finish")
             else:
