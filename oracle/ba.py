@@ -30,7 +30,7 @@ def bundle_adjustment(
     poses, disps, disps_sens, intrinsics, rig, target, weight, disp_damping, ii, jj, t0, t1, n_iters,
     pose_damping, pose_ep, motion_only=False, limited_disp=False, optimize_intrinsics=False,
     optimize_rig_rotation=False, model="pinhole", alpha=0.001, dtype=np.float64, solver="dense",
-    cross_view_idx=None, return_debug=False, weight_scale=0.001, intrinsics_factor=8.0, mutate=(),
+    cross_view_idx=None, return_debug=False, weight_scale=0.001, intrinsics_factor=8.0, mutate=(), solve=None,
 ):
     """buffer.py:373-525.
 
@@ -44,6 +44,11 @@ def bundle_adjustment(
     `mutate` names deliberate errors, for the tests that prove a case can tell them apart (tests/test_oracle_ba_cases.py);
     empty, nothing changes: "no_valid" drops the validity mask, "abs_reject" rejects |dz| > 10 instead of dz > 10,
     "no_clamp" leaves out the final clamp, "fix_target_only" also fixes poses outside [t0, t1) that are only targets.
+
+    `solve`: a callable (S, g) -> dx in place of numpy.linalg.solve on the damped reduced system, for the tests that put a
+    wrong solver behind the same normal equations (oracle/solver_cases.py:defects); None, nothing changes.  A callable
+    with a true attribute `with_diag` is called as (S, g, diagonal of H before the damping) - what a solver that damps the
+    system itself, as the device's do, has at hand.
     """
     dt = np.dtype(dtype)
     poses = np.array(poses, dtype=dt)
@@ -153,6 +158,7 @@ def bundle_adjustment(
             wv[k] += -dt.type(alpha) * (dflat[k] - sens[k])
 
         # damping (solver.py:161-164; matrix.py:179-192, 346-358)
+        Hdiag = np.diag(H).copy()
         for kind, idx, dim in blocks:
             o, _d = off[(kind, idx)]
             lam, ep = {"pose": (pose_damping, pose_ep), "intr": (1e-6, 1e-6), "rig": (1e-4, 1e-4)}[kind]
@@ -178,7 +184,9 @@ def bundle_adjustment(
                     S[oa:oa + da, ob:ob + db] -= EQ @ Eblk[(b, k)].T
 
         if n > 0:
-            if solver == "spsolve":  # solver.py:33-44: fp32 COO -> CSR -> SuperLU
+            if solve is not None:
+                dx = np.asarray(solve(S, gv, Hdiag) if getattr(solve, "with_diag", False) else solve(S, gv), dtype=dt)
+            elif solver == "spsolve":  # solver.py:33-44: fp32 COO -> CSR -> SuperLU
                 from scipy.sparse import coo_matrix
                 from scipy.sparse.linalg import spsolve
                 nz = np.nonzero(S)

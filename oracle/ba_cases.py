@@ -288,9 +288,9 @@ def oracle_run(name, dtype="float64", debug=False):
     return ba.bundle_adjustment(*args, dtype=np.dtype(dtype), return_debug=debug, **kw)
 
 
-def counts(name):
-    """(free poses, free disparity frames, unknowns) from the oracle's sets: what the plan reports in info[0], [1], [3]"""
-    c = case(name)
+def case_counts(c):
+    """(free poses, free disparity frames, unknowns) of a case namespace from the oracle's sets: what the plan reports in
+    info[0], [1], [3]"""
     g = c.g
     V = g.V if c.rig else 1
     pi, qi, di, pj, qj = terms(c)
@@ -303,15 +303,28 @@ def counts(name):
     return len(free), len(np.unique(di)), 6 * len(free) + tail
 
 
-def step_bounds(name):
-    """The tolerance of the GPU test, relative to the step: per output, 4 x delta32 - the elementwise-maximum distance
-    between the oracle in float32 (the reference's arithmetic) and in float64 (exact) on this case - and never looser than
-    the suite's 1e-4 form (1e-4 max(1, |p|), 1e-4 max|d|, 1e-4 max|k|, 1e-4 for the rig).
-    -> dict output -> (delta32, bound), outputs in the order poses, disps, intr, rig."""
-    o64, o32 = oracle_run(name, "float64"), oracle_run(name, "float32")
+def counts(name):
+    """`case_counts` of the named case"""
+    return case_counts(case(name))
+
+
+OUTPUTS = ("poses", "disps", "intr", "rig")
+
+
+def output_bounds(o64, o32, factor=4, ulps=0):
+    """Per output of the oracle (poses, disps, intrinsics, rig): delta32 = the elementwise-maximum distance between its
+    float32 run (the reference's arithmetic) and its float64 run (exact), and the bound min(factor x delta32, the suite's
+    1e-4 form: 1e-4 max(1, |p|), 1e-4 max|d|, 1e-4 max|k|, 1e-4 for the rig), not below `ulps` units in the last place of
+    the largest float32 value of the output.  Nothing but the oracle enters.  -> dict output -> (delta32, bound)"""
     old = (1e-4 * max(1.0, np.abs(o64[0]).max()), 1e-4 * np.abs(o64[1]).max(), 1e-4 * np.abs(o64[2]).max(), 1e-4)
     out = {}
-    for key, a, b, lim in zip(("poses", "disps", "intr", "rig"), o32, o64, old):
+    for key, a, b, lim in zip(OUTPUTS, o32, o64, old):
         d32 = float(np.abs(a.astype(F8) - b).max())
-        out[key] = (d32, min(4 * d32, lim))
+        out[key] = (d32, max(min(factor * d32, lim), ulps * 2.0 ** -23 * float(np.abs(b).max())))
     return out
+
+
+def step_bounds(name):
+    """The tolerance of the GPU test, relative to the step: per output, 4 x delta32 on this case and never looser than the
+    suite's 1e-4 form (`output_bounds`).  -> dict output -> (delta32, bound), outputs in the order poses, disps, intr, rig."""
+    return output_bounds(oracle_run(name, "float64"), oracle_run(name, "float32"))

@@ -1,6 +1,6 @@
 """The dense BA on the device off the smooth trajectory: pixels behind the camera, pixels / edges / frames without weight,
 rejected and clamped disparity steps, ragged plans, source frames of 7 / 9 / 17 terms, M > 4096 terms, more than 1024
-disparity frames - and a factorisation that fails.
+disparity frames - and a factorisation that fails, in each of the four solvers.
 
 Cases: oracle/ba_cases.py (tests/test_oracle_ba_cases.py proves on the CPU what each one reaches, that none sits on a
 branch, and that an oracle with one branch wrong leaves the tolerance used here).  Tolerance, relative to the STEP: per
@@ -10,68 +10,23 @@ the suite's 1e-4 form (`ba_cases.step_bounds`).  Every call works in buffers wit
 """
 
 import os
+from types import SimpleNamespace
 
 import numpy as np
 import pytest
 import torch
 
+from ba_device import T, check_outputs, run_case
+from ba_device import option_sets as _option_sets
 from oracle import ba_cases as bc
+from oracle import ba_route as br
 from oracle import se3 as ose3
+from oracle import solver_cases as sc
 from vipe_amd.synth import expand_edges, make_graph
 
 pytestmark = pytest.mark.gpu
 
 GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
-GUARD = 2  # frames beyond the graph in the pose and disparity buffers
-
-
-def dev():
-    assert torch.cuda.is_available(), "these tests need the MI355X"
-    return torch.device("cuda:0")
-
-
-def T(x):
-    return torch.from_numpy(np.ascontiguousarray(x)).to(dev())
-
-
-def _padded(a, rows, fill):
-    """[rows + extra, ...] float32: `a` and then sentinel rows cycling through `fill`"""
-    a = np.asarray(a, np.float32)
-    tail = np.resize(np.asarray(fill, np.float32), (rows,) + a.shape[1:])
-    return np.concatenate([a, tail])
-
-
-def run_case(c, opts=0):
-    """`slam_ext.dense_ba` on a case, in buffers of n + GUARD poses / (n + GUARD) V frames.  The sentinel poses must keep
-    their bits; the sentinel disparities (0.5 and 1e-5 in turn) change only by the clamp at 1e-3 of the whole buffer
-    (buffer.py:525).  -> poses [n,7], disps like g.disps, intrinsics, rig, info"""
-    from vipe_amd.ext import slam_ext
-    g = c.g
-    V = g.V if c.rig else 1
-    n, ht, wd = g.n, g.ht, g.wd
-    pi, qi, di, pj, qj = expand_edges(g.ii, g.jj, V)
-    M = len(pi)
-    flat = lambda a: np.asarray(a).reshape(n * V, ht, wd)
-    sentinel_pose = np.array([[0.3, -0.2, 0.1, 0.5, -0.5, 0.5, 0.5], [7.0, 8.0, 9.0, 0.0, 0.6, 0.0, 0.8]], np.float32)
-    poses = T(_padded(g.poses, GUARD, sentinel_pose))
-    disps = T(_padded(flat(g.disps), GUARD * V, [0.5, 1e-5]))
-    sens = T(_padded(flat(g.disps_sens), GUARD * V, [0.0]))
-    eta = T(_padded(flat(g.eta), GUARD * V, [0.01]))
-    intr = T(c.intr).clone()
-    rig = T(g.rig if c.rig else ose3.se3_identity(1)).clone()
-    tail_p, tail_d = poses[n:].clone(), disps[n * V:].clone()
-    info = slam_ext.dense_ba(poses, disps, sens, intr, rig, T(g.target.reshape(M, -1, 2)), T(g.weight.reshape(M, -1, 2)), eta,
-                             T(pi), T(qi), T(pj), T(qj), T(di), camera=c.cam, want_info=True, solver_options=opts, **c.bk)
-    torch.cuda.synchronize()
-    assert torch.equal(poses[n:].view(torch.int32), tail_p.view(torch.int32)), "a pose beyond the graph was written"
-    assert torch.equal(disps[n * V:], tail_d.clamp(min=1e-3)), "disparities beyond the graph: only the 1e-3 clamp may act"
-    return (poses[:n].cpu().numpy(), disps[:n * V].cpu().numpy().reshape(g.disps.shape), intr.cpu().numpy(),
-            rig.cpu().numpy(), info.cpu().numpy())
-
-
-def _option_sets():
-    from vipe_amd.ext import slam_ext
-    return {"default": 0, "general": slam_ext.BA_OPT_ONE_CHAIN | slam_ext.BA_OPT_GENERAL_ACCUMULATE}
 
 
 def _check(name, tag, got):
@@ -84,14 +39,7 @@ def _check(name, tag, got):
     n_free, n_fd, n_unknown = bc.counts(name)
     assert info[2] == 0, "Cholesky must not fail"
     assert (info[0], info[1], info[3]) == (n_free, n_fd, n_unknown), info
-    outs = {"poses": p, "disps": d.reshape(o64[1].shape), "intr": k, "rig": r}
-    errs = {}
-    for (key, (d32, bound)), ref in zip(bounds.items(), o64):
-        errs[key] = float(np.nan_to_num(np.abs(outs[key].astype(np.float64) - ref), nan=np.inf).max())
-        ratio = errs[key] / d32 if d32 > 0 else (0.0 if errs[key] == 0 else np.inf)
-        print(f"{name} [{tag}] {key}: kernel error {errs[key]:.3g}, delta32 {d32:.3g}, ratio {ratio:.3g}, bound {bound:.3g}")
-    for key, (d32, bound) in bounds.items():
-        assert errs[key] <= bound, (name, tag, key, errs[key], d32, bound)
+    check_outputs(name, tag, got, o64, bounds)
     G = np.load(os.path.join(GOLD, "ba_edges_reference.npz"))
     rp, rd, rk, rr = (G[f"{name}/{x}"] for x in ("poses", "disps", "intrinsics", "rig"))
     assert np.abs(p - rp).max() <= 1e-4 * max(1.0, np.abs(rp).max())
@@ -116,31 +64,48 @@ def test_dense_ba_rig_of_more_than_1024_disparity_frames():
     _check("rig8_n129", "default", run_case(bc.case("rig8_n129")))
 
 
-@pytest.mark.parametrize("kind", ["band", "dense", "global"])
-def test_dense_ba_failed_factorisation_takes_a_zero_step(kind):
-    """One NaN in a target, at a pixel with weight, on the three graphs of
-    test_dense_ba_path_hints_across_calls_with_one_plan (band solver, LDS dense solver, tiled Cholesky), two iterations in
-    one call.  "Zero step on a failed factorisation": the failure is counted, the solver that owns the system is the one
-    that reports, no pose moves, and every disparity comes back finite and >= 1e-3 (the pixels the NaN reached are set to
-    the clamp value)."""
-    from vipe_amd.ext import slam_ext
+def _failing_case(kind):
+    """the graphs of test_dense_ba_path_hints_across_calls_with_one_plan, pose-only, and the two single-workgroup systems
+    of oracle/solver_cases.py (n = 175 with the focal length; the rig with intrinsics and rig rotations, n = 254)"""
+    if kind.startswith("one_workgroup"):
+        return sc.case({"one_workgroup": "wg175", "one_workgroup_rig": "wg254_rig"}[kind])
     g = {"band": lambda: make_graph(n=14, height=96, width=128, radius=2, seed=71),
          "dense": lambda: make_graph(n=20, height=96, width=128, radius=19, seed=91),
          "global": lambda: make_graph(n=70, height=96, width=128, radius=3, extra_edges=260, seed=101)}[kind]()
-    n, E, P = len(g.poses), len(g.ii), g.ht * g.wd
-    e, px = E // 2, P // 2
-    tgt, w = g.target.reshape(E, P, 2).copy(), g.weight.reshape(E, P, 2)
-    assert w[e, px, 0] > 0.01 and w[e, px, 1] > 0.01 and 1 <= g.ii[e] < n and 1 <= g.jj[e] < n
+    return SimpleNamespace(g=g, cam="pinhole", intr=g.intrinsics, rig=False,
+                           bk=dict(t0=1, t1=g.n, n_iters=2, pose_damping=1e-3, pose_ep=0.1))
+
+
+@pytest.mark.parametrize("kind", ["band", "dense", "global", "one_workgroup", "one_workgroup_rig"])
+def test_dense_ba_failed_factorisation_takes_a_zero_step(kind):
+    """One NaN in a target, at a pixel with weight, on the three graphs of
+    test_dense_ba_path_hints_across_calls_with_one_plan (band solver, LDS dense solver, tiled Cholesky) and on two systems
+    of the single-workgroup global-memory Cholesky (its `sh.fail` path; mono with the focal length, and a rig with eight
+    tail rows), two iterations in one call.  "Zero step on a failed factorisation": the failure is counted, the solver that
+    owns the system is the one that reports, no pose (intrinsic, rig transform) moves, and every disparity comes back
+    finite and >= 1e-3 (the pixels the NaN reached are set to the clamp value)."""
+    from vipe_amd.ext import slam_ext
+    c = _failing_case(kind)
+    g, V = c.g, (c.g.V if c.rig else 1)
+    pi, qi, di, pj, qj = expand_edges(g.ii, g.jj, V)
+    n, M, P = len(g.poses), len(pi), g.ht * g.wd
+    e, px = M // 2, P // 2
+    tgt, w = g.target.reshape(M, P, 2).copy(), g.weight.reshape(M, P, 2)
+    assert w[e, px, 0] > 0.01 and w[e, px, 1] > 0.01 and 1 <= pi[e] < n and 1 <= pj[e] < n
     tgt[e, px, 0] = np.nan
-    z = np.zeros_like(g.ii)
-    poses, disps = T(g.poses).clone(), T(g.disps).clone()
-    info = slam_ext.dense_ba(poses, disps, T(g.disps_sens), T(g.intrinsics), T(ose3.se3_identity(1)), T(tgt), T(w), T(g.eta),
-                             T(g.ii), T(z), T(g.jj), T(z), T(g.ii), want_info=True, t0=1, t1=n, n_iters=2, pose_damping=1e-3,
-                             pose_ep=0.1)
+    if kind.startswith("one_workgroup"):
+        assert br.global_form(*sc.route_args(c.name)) == "one_workgroup"
+    rig0 = g.rig if c.rig else ose3.se3_identity(1)
+    poses, disps, intr, rig = T(g.poses).clone(), T(g.disps.reshape(n * V, g.ht, g.wd)).clone(), T(c.intr).clone(), T(rig0).clone()
+    info = slam_ext.dense_ba(poses, disps, T(g.disps_sens.reshape(n * V, g.ht, g.wd)), intr, rig, T(tgt), T(w),
+                             T(g.eta.reshape(n * V, g.ht, g.wd)), T(pi), T(qi), T(pj), T(qj), T(di), camera=c.cam, want_info=True,
+                             **c.bk)
     torch.cuda.synchronize()
     info, p, d = info.cpu().numpy(), poses.cpu().numpy(), disps.cpu().numpy()
     print(kind, "info", info, "max pose change", np.abs(p - g.poses).max(), "non-finite disparities", (~np.isfinite(d)).sum())
     assert info[2] >= 1, info
-    assert info[5] == {"band": 1, "dense": 2, "global": 0}[kind], info
+    assert info[5] == {"band": 1, "dense": 2, "global": 0, "one_workgroup": 0, "one_workgroup_rig": 0}[kind], info
     assert np.isfinite(p).all() and np.abs(p - g.poses).max() <= 1e-6
     assert np.isfinite(d).all() and d.min() >= 1e-3
+    k, r = intr.cpu().numpy(), rig.cpu().numpy()
+    assert np.array_equal(k, c.intr) and np.isfinite(r).all() and np.abs(r - rig0).max() <= 1e-6

@@ -11,6 +11,7 @@ import pytest
 import torch
 
 from oracle import ba as oba
+from oracle import ba_route as oroute
 from oracle import corr as ocorr
 from oracle import geom as ogeom
 from oracle import se3 as ose3
@@ -1912,12 +1913,7 @@ def band_solver_form(info, two_chain=True):
     nb, n, bandblk = int(info[0]), int(info[3]), int(info[4])
     F = n - 6 * nb
     assert 0 <= F <= 2, f"the band solver takes at most two intrinsics columns, not {F}"
-    PB = 6 * bandblk
-    npair = PB * (PB + 1) // 2 + (F + 1) * PB + (0, 2, 5)[F]
-    wide = PB + 7 > 64 or npair > 917  # 917 = 21 + 2 * (512 - 64): the pairs two slots per thread hold
-    if not wide and F == 0 and two_chain and bandblk >= 1 and nb >= 4 * bandblk + 4:
-        return "two_chain"
-    return "wide" if wide else "narrow"
+    return oroute.band_form(n, nb, bandblk, F, 0, band2=two_chain)  # the whole rule, LDS limits included: oracle/ba_route.py
 
 
 @pytest.mark.parametrize("n,radius,cam,intr,form,PB", [
