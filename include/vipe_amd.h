@@ -911,6 +911,72 @@ int vipe_cloud_resolve(const int64_t* d_zbuf, int B, int H0, int W0, void* d_dep
                        void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Hole-free depth maps: grid kNN scale / shift completion (depth_complete.hip).  A sparse map - values at some pixels, 0
+ * elsewhere, such as the fused surface vipe_cloud_resolve draws - and a dense prediction of the same size: every pixel
+ * without a sparse value takes the prediction there, aligned to the K nearest pixels that hold both by an
+ * inverse-distance-weighted least-squares fit of scale and shift in the disparity domain.  It is the network-free first
+ * step of the reference's map-prompted depth path (priorda/depth_completion.py:246-379, `kss_completer`), restated for
+ * points that are pixels of one grid; tests/depth_complete_reference.py restates it in float64.
+ *
+ * Per image b of B: sparse[b], pred[b] [H,W] of one dtype (VIPE_F16 / VIPE_F32), mask[b] [H,W] u8 or none.
+ *   domain  VIPE_COMPLETE_DISP: the values are disparities.  VIPE_COMPLETE_DEPTH: depths; each value that enters the fit
+ *           becomes a disparity by one IEEE 1.0f / x on load, and the result goes back by one 1.0f / r, rounded once to
+ *           the output dtype
+ *   anchor  sparse and pred are both finite and > 0 at the pixel (both are needed for the fit)
+ *   target  not an anchor, pred finite and > 0, and mask NULL or non-zero there
+ *   output  an anchor: its sparse value, copied bit for bit;  a target: the completion below;  neither: 0
+ * Neighbours of a target (y, x): the anchors at offsets (dy, dx) with d2 = dy^2 + dx^2 <= R^2 - with wrap_x dx is the
+ * signed column offset of smallest magnitude, the columns being a circle - of which the k' <= K smallest by the key
+ * (d2, dy, dx), compared lexicographically, are taken.  Without wrap_x that is "smaller distance, then lower row-major
+ * index", the tie rule of vipe_nearest_neighbours.  The tie rule is part of the result: on a pixel grid ties at the K-th
+ * place are common, and the order of the reference's kd-tree is unspecified.
+ * Fit, in f32, every product and sum rounded on its own, neighbours in key order, p the prediction's and d the sparse
+ * map's disparity at a neighbour, sums starting with the first neighbour:
+ *   w = 1.0f / float(d2)      the square of the reference's 1 / dist: the reference scales the ROWS of the system by its
+ *                             weights before lstsq, so the squares weigh the residuals; its division by sum(w) cancels
+ *   S = sum w;  pm = (sum w p) / S;  dm = (sum w d) / S;  e = p - pm;  f = d - dm
+ *   var = sum (w e) e;  cov = sum (w e) f;  thr = ((2^-10 pm) (2^-10 pm)) S
+ *   k' >= 2, var > thr and s = cov / var > 0:  affine, t = dm - s pm;   otherwise scale only: s = dm / pm, t = 0
+ *   r = s p(y, x) + t
+ * The two guards are this library's: the reference adds 1e-5 * rand to the predictions to dodge rank deficiency (so its
+ * result is not a function of its input) and accepts negative scales (which turn the prediction's order around).
+ * r not finite or <= 0: the output is 0, the pixel is REJECTED.  k' = 0: the output is 0, the pixel is UNREACHED.  In the
+ * depth domain 1.0f / r of a subnormal r is +inf, and an f16 output can round to +inf or 0: the value is stored as it is.
+ * Not built: a cap on |s|, a search beyond R, a confidence that gates the prediction.
+ *   K 1..8;  radius R 1..64;  wrap_x 0 | 1 (the panorama), which needs W >= 2R + 1;  H, W <= 2^24, H W <= 2^31 - 1
+ *   d_out [B,H,W] of dtype
+ *   d_scale, d_shift [B,H,W] f32 or NULL: (s, t) at an affine or scale-only target, (1, 0) at an anchor, (0, 0) elsewhere
+ *          (unreached and rejected targets included)
+ *   d_nbr [B,H,W,K] int32 or NULL: at a target the neighbours' row-major pixel indices y W + x in key order, padded
+ *          with -1 (a rejected target lists the neighbours it was fitted to); all -1 elsewhere
+ *   d_stats [4] int64, added to: targets with an affine fit, with a scale-only fit, unreached, rejected - every target
+ *          counts exactly once.  Summed per wave and per workgroup first.
+ * Apart from the counters there are no atomics: the outputs are a function of the inputs, bit for bit, whatever the
+ * batch split, the run, or what the output buffers held.
+ *
+ * vipe_depth_anchor_bits packs the anchor test: d_bits [B,H,ceil(W/64)] uint64 in int64 storage, bit (x & 63) of word
+ * x >> 6; bits of columns past W are 0.  One wave ballot per word.  vipe_depth_complete reads the anchors from d_bits
+ * alone (and masks off what a stale buffer may hold past W): without the pass every workgroup would read a
+ * (tile + 2R)^2 window of both value maps.
+ * vipe_depth_complete: one thread per pixel, 64 x 4 tiles, the image in grid.y.  The workgroup stages the bits of its
+ * rows and a halo of R (columns: the three words around the tile; with wrap_x taken modulo W) in LDS, 3168 bytes at
+ * R = 64.  A target scans rows dy = 0, -1, 1, -2, 2, .. until dy^2 exceeds its K-th best d2 (R^2 while it holds fewer
+ * than K), in a row only |dx| <= floor(sqrt(kth - dy^2)), walking set bits; the K best keys d2 << 16 | (dy + R) << 8 |
+ * (dx + R) stay sorted in registers.  Only the final k' neighbours' values are gathered from memory.
+ * Both: B <= 65535; B == 0 is VIPE_OK without a launch; the value maps, d_bits, d_out and d_stats non-null otherwise;
+ * anything else is VIPE_EINVAL.
+ * ------------------------------------------------------------------------------------------- */
+#define VIPE_COMPLETE_DISP 0
+#define VIPE_COMPLETE_DEPTH 1
+
+int vipe_depth_anchor_bits(const void* d_sparse, const void* d_pred, int dtype, int B, int H, int W, int64_t* d_bits,
+                           void* stream);
+
+int vipe_depth_complete(const void* d_sparse, const void* d_pred, int dtype, const unsigned char* d_mask,
+                        const int64_t* d_bits, int B, int H, int W, int domain, int K, int radius, int wrap_x, void* d_out,
+                        float* d_scale, float* d_shift, int* d_nbr, int64_t* d_stats, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Sparse keypoint tracker: corner detection and pyramidal Lucas-Kanade (klt_track.hip), the producer of the tracks
  * that `SparseTracks` feeds to the motion filter and to the BA's second flow term.  An addition: the reference's only
  * real tracker wraps a closed CUDA package.  tests/klt_reference.py restates this arithmetic in float64.

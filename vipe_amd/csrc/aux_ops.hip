@@ -629,15 +629,19 @@ __global__ __launch_bounds__(256) void nearest_kernel(const float* __restrict__ 
       const float dx = qx - p.x, dy = qy - p.y, dz = qz - p.z;
       const float d = dx * dx + dy * dy + dz * dz;
       if (d < bd[NN_KMAX - 1] && (knn == NN_KMAX || d < bd[knn - 1])) {
-        // insertion into the ascending list (strict <: an equal distance keeps the earlier, i.e. lower, index first)
+        // insertion into the ascending list (strict <: an equal distance keeps the earlier, i.e. lower, index first).
+        // Once the new point has found its place everything behind it moves down one place, equal distances included:
+        // comparing the displaced entry again would let it jump over - and push out - an equal one with a higher index
         float cd = d;
         int ci = (int)(t0 + i);
+        bool placed = false;
 #pragma unroll
         for (int k = 0; k < NN_KMAX; ++k) {
-          if (k < knn && cd < bd[k]) {
+          if (k < knn && (placed || cd < bd[k])) {
             const float td = bd[k]; const int ti = bi[k];
             bd[k] = cd; bi[k] = ci;
             cd = td; ci = ti;
+            placed = true;
           }
         }
       }

@@ -17,6 +17,9 @@ vipe/streams/base.py:164-254), intrinsics rescaled on the way in and recovered t
     cloud_render(..)           the way back into the cameras (`vipe_cloud_render`): points splatted into a 64-bit
                                z-buffer (`cloud_zbuffer`) on that grid; `cloud_resolve` (`vipe_cloud_resolve`) makes
                                depth, colour and index images of it
+    depth_complete(..)         the last link (`vipe_depth_anchor_bits` + `vipe_depth_complete`): a sparse map - those
+                               images - where it has values, elsewhere a dense prediction aligned to the K nearest sparse
+                               samples by a weighted scale / shift fit in the disparity domain
 
 Decoding stays with the caller: frames arrive as tensors.  The nearest-neighbour `instance` channel of `VideoFrame` is
 not read by the SLAM path and is not carried."""
@@ -368,6 +371,78 @@ def cloud_resolve(zbuf, rgb_points=None, dtype=torch.float16, want_index=False):
                                    ptr(rgb_points) if M else None, M, ptr(rgb), ptr(index), stream_ptr(zbuf)),
           "vipe_cloud_resolve")
     return depth, rgb, index
+
+
+_COMPLETE_DOMAIN = {"disp": 0, "depth": 1}  # VIPE_COMPLETE_*
+_ANCHOR_BITS = {}  # (device, stream) -> int64 buffer the anchor bits of `depth_complete` are packed into, grown on demand
+
+
+def _anchor_bits(n, device):
+    """one buffer per device and stream: calls on one stream are ordered, so the next call may overwrite it"""
+    key = (device, torch.cuda.current_stream(device).cuda_stream)
+    buf = _ANCHOR_BITS.get(key)
+    if buf is None or buf.numel() < n:
+        buf = _ANCHOR_BITS[key] = torch.empty(n, dtype=torch.int64, device=device)
+    return buf[:n]
+
+
+def depth_complete(sparse, pred, K=5, radius=32, domain="depth", mask=None, wrap_x=False, out=None, want_fit=False,
+                   want_neighbours=False, stats=None):
+    """A sparse map completed by a dense prediction, one `vipe_depth_anchor_bits` and one `vipe_depth_complete` launch
+    (the rule is in include/vipe_amd.h): where `sparse` and `pred` are both finite and positive - an anchor - the output is
+    the sparse value, bit for bit; at every other pixel with a finite positive prediction (and `mask` non-zero, when one
+    is given) it is s * pred + t in the disparity domain, (s, t) fitted to the `K` nearest anchors within `radius` pixels
+    (ties: smaller distance, then lower row offset, then lower column offset) by least squares weighted with
+    1 / distance^2 - affine where the neighbours' predictions vary and the scale comes out positive, scale only
+    otherwise; 0 where no anchor is in reach, where the result is not positive, and where there is no prediction.
+    Images are completed independently of each other.  Nothing but the counters is atomic: the same inputs give the same
+    bits.
+
+    sparse, pred [B,H,W] fp16 / fp32 of one dtype; K 1..8; radius 1..64; domain "depth" (the values are depths: fitted
+    as 1 / x, returned as 1 / r) or "disp"; mask [B,H,W] bool / uint8 or None; wrap_x: the columns are a circle (the
+    panorama; needs W >= 2 * radius + 1); out [B,H,W] of that dtype (fresh when None; what it held does not matter);
+    stats [4] int64 += (affine, scale-only, unreached, rejected targets), a fresh one when None.  Device tensors only.
+    The single route from Python to the two kernels; the bit buffer is kept per device and reused.
+    -> (out, scale [B,H,W] fp32 or None, shift likewise (`want_fit`; (1, 0) at anchors, (0, 0) where the output is 0 for
+    lack of a fit), neighbours [B,H,W,K] int32 or None (`want_neighbours`; pixel indices y * W + x in key order, -1
+    padded), stats)"""
+    if not (sparse.is_cuda and pred.is_cuda):
+        raise NotImplementedError("depth_complete: device tensors only (vipe_depth_complete is a HIP kernel)")
+    require(sparse.dim() == 3 and sparse.dtype in (torch.float16, torch.float32) and sparse.is_contiguous(),
+            "sparse: contiguous [B,H,W] fp16 / fp32")
+    B, H, W = (int(v) for v in sparse.shape)
+    require(pred.device == sparse.device and pred.dtype == sparse.dtype and pred.is_contiguous() and tuple(pred.shape) == (B, H, W),
+            f"pred: contiguous [{B},{H},{W}] of sparse's dtype on its device")
+    require(H > 0 and W > 0 and H <= 1 << 24 and W <= 1 << 24 and H * W <= 2 ** 31 - 1 and B <= 65535,
+            "images of a positive size, sides up to 2^24, fewer than 2^31 pixels each; at most 65535 of them")
+    require(1 <= int(K) <= 8, "K: 1 to 8")
+    require(1 <= int(radius) <= 64, "radius: 1 to 64")
+    require(domain in _COMPLETE_DOMAIN, f"domain: one of {sorted(_COMPLETE_DOMAIN)}")
+    require(not wrap_x or W >= 2 * int(radius) + 1, "wrap_x: the image must be at least 2 * radius + 1 columns wide")
+    if mask is not None:
+        require(mask.is_cuda and mask.device == sparse.device and mask.dtype in (torch.bool, torch.uint8) and mask.is_contiguous()
+                and tuple(mask.shape) == (B, H, W), f"mask: contiguous [{B},{H},{W}] bool / uint8 on sparse's device")
+    dev, K = sparse.device, int(K)
+    if out is None:
+        out = torch.empty((B, H, W), dtype=sparse.dtype, device=dev)
+    require(out.is_cuda and out.device == dev and out.dtype == sparse.dtype and out.is_contiguous() and tuple(out.shape) == (B, H, W),
+            f"out: contiguous [{B},{H},{W}] of sparse's dtype on its device")
+    if stats is None:
+        stats = torch.zeros(4, dtype=torch.int64, device=dev)
+    require(stats.is_cuda and stats.device == dev and stats.dtype == torch.int64 and stats.is_contiguous()
+            and tuple(stats.shape) == (4,), "stats: contiguous int64 [4] on sparse's device")
+    scale = torch.empty((B, H, W), dtype=torch.float32, device=dev) if want_fit else None
+    shift = torch.empty((B, H, W), dtype=torch.float32, device=dev) if want_fit else None
+    nbr = torch.empty((B, H, W, K), dtype=torch.int32, device=dev) if want_neighbours else None
+    if B == 0:
+        return out, scale, shift, nbr, stats
+    code = F16 if sparse.dtype == torch.float16 else F32
+    bits = _anchor_bits(B * H * ((W + 63) // 64), dev)
+    check(lib().vipe_depth_anchor_bits(ptr(sparse), ptr(pred), code, B, H, W, ptr(bits), stream_ptr(sparse)), "vipe_depth_anchor_bits")
+    check(lib().vipe_depth_complete(ptr(sparse), ptr(pred), code, ptr(mask), ptr(bits), B, H, W, _COMPLETE_DOMAIN[domain], K,
+                                    int(radius), int(bool(wrap_x)), ptr(out), ptr(scale), ptr(shift), ptr(nbr), ptr(stats),
+                                    stream_ptr(sparse)), "vipe_depth_complete")
+    return out, scale, shift, nbr, stats
 
 
 def nearest_keyframes(frame_tstamps, kf_tstamps, kf_valid, k):

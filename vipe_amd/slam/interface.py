@@ -87,7 +87,9 @@ def rescale_frame_depths(frame_depths, s):
     factor `s` the way `FilledReturn.scale` does it (disparities / s, translations * s): depths * s.  `run` itself
     applies no metric rescaling, so the maps are in the trajectory's units until this is applied.  -> a new tensor of
     the same dtype (fp16 maps are scaled in fp32 and rounded once).  It fits `SLAMOutput.fused_depths` (and the maps of
-    a `fused_depth_sink`) as it is: they are depths in the same units, and an empty pixel's 0 stays 0."""
+    a `fused_depth_sink`) as it is: they are depths in the same units, and an empty pixel's 0 stays 0.  So it does
+    `SLAMOutput.complete_depths` (and the maps of a `complete_depth_sink`): scale and shift are fitted between two maps
+    in those units, so the completed depth scales with them."""
     return (frame_depths.float() * s).to(frame_depths.dtype)
 
 
@@ -201,11 +203,19 @@ class SLAMOutput:
     (`SLAMConfig.frame_depth_dtype`), pixel for pixel beside `frame_depths`: the fused cloud drawn into every frame's
     camera with the final poses (`FusedCloud.render`), 0 where nothing is drawn, in the trajectory's units
     (`rescale_frame_depths` for a metric factor); with `SLAMConfig.fused_depth_color` `fused_rgb` [T,V,H0,W0,3] uint8, the
-    colour of the point each pixel shows."""
+    colour of the point each pixel shows.
+
+    None unless `SLAMConfig.complete_depth`: `complete_depths` [T,V,H0,W0] (`SLAMConfig.frame_depth_dtype`; None when a
+    `complete_depth_sink` took the maps), `fused_depths` without holes: the fused value where there is one, elsewhere the
+    frame's own depth aligned to the nearest fused pixels (`ingest.depth_complete`), 0 where neither can be had
+    (`rescale_frame_depths` for a metric factor); and `complete_depth_stats`, the clip's counters of filled pixels:
+    a dict of affine, scale_only, unreached, rejected."""
 
     def __init__(self, *, trajectory, intrinsics, rig=None, slam_map=None, ba_residual=0.0, keyframe_disps_up=None,
                  keyframe_disps_up_valid=None, keyframe_disp_var=None, keyframe_pose_cov=None, frame_depths=None,
-                 frame_disps_lowres=None, frame_depth_conf=None, fused_cloud=None, fused_depths=None, fused_rgb=None):
+                 frame_disps_lowres=None, frame_depth_conf=None, fused_cloud=None, fused_depths=None, fused_rgb=None,
+                 complete_depths=None, complete_depth_stats=None):
+        self.complete_depths, self.complete_depth_stats = complete_depths, complete_depth_stats
         self.fused_depths, self.fused_rgb = fused_depths, fused_rgb
         self.frame_depths, self.frame_disps_lowres = frame_depths, frame_disps_lowres
         self.frame_depth_conf, self.fused_cloud = frame_depth_conf, fused_cloud

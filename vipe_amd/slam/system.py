@@ -94,6 +94,16 @@ class SLAMConfig:
     fused_depth_color: bool = False        # `SLAMOutput.fused_rgb` beside the maps (needs `fused_cloud_color`)
     fused_depth_sink: object = None        # callable (frame_idx, view_idx, depth [H0,W0] device tensor), in frame order
                                            # (`driver.artifacts.DepthZipWriter`); `fused_depths` then stays None
+    complete_depth: bool = False   # hole-free fused maps (`SLAMOutput.complete_depths`): `fused_depths` where they
+                                   # exist, elsewhere the frame's own `frame_depths` aligned to the nearest fused samples
+                                   # (scale and shift in the disparity domain, `ingest.depth_complete`); per pass-2 chunk one
+                                   # `vipe_depth_anchor_bits` and one `vipe_depth_complete` launch right after the resolve.
+                                   # Needs `fused_depth` and both kinds of maps kept (no `frame_depth_sink`, no
+                                   # `fused_depth_sink`).  It only reads.  Off: nothing is allocated, no launch differs
+    complete_depth_k: int = 5              # fused samples a pixel is aligned to (1 to 8), nearest first
+    complete_depth_radius: int = 32        # how far, in pixels, a sample may lie (1 to 64); no sample in reach: the pixel stays 0
+    complete_depth_sink: object = None     # callable (frame_idx, view_idx, depth [H0,W0] device tensor), in frame order;
+                                           # `complete_depths` then stays None
     sparse_tracks: str = None     # "klt": `run` builds a `KLTSparseTracks(n_views)` (corners + pyramidal Lucas-Kanade in
                                    # HIP) when the caller passed no tracker - the motion filter's track score and the BA's
                                    # track term get real tracks.  None: no tracker is built, nothing is launched or changed
@@ -144,6 +154,14 @@ class SLAMSystem:
             assert 0 <= int(c.fused_depth_max_radius) <= 4, "SLAMConfig.fused_depth_max_radius: 0 to 4"
             assert not c.fused_depth_color or c.fused_cloud_color, \
                 "SLAMConfig.fused_depth_color shows the cloud's colours: set fused_cloud_color=True as well"
+        if self.config.complete_depth:
+            c = self.config
+            assert c.fused_depth, "SLAMConfig.complete_depth fills the holes of fused_depth's maps: set fused_depth=True as well"
+            assert c.frame_depth_sink is None, \
+                "SLAMConfig.complete_depth reads the frame maps again after the cloud is extracted: they must be kept (no frame_depth_sink)"
+            assert c.fused_depth_sink is None, "SLAMConfig.complete_depth needs the fused maps kept (no fused_depth_sink)"
+            assert 1 <= int(c.complete_depth_k) <= 8, "SLAMConfig.complete_depth_k: 1 to 8"
+            assert 1 <= int(c.complete_depth_radius) <= 64, "SLAMConfig.complete_depth_radius: 1 to 64"
         self._config_tracker = sparse_tracks is None and self.config.sparse_tracks == "klt"  # then a fresh one per run
         self._resizes = None  # one `StandardResize` per view inside `run(..., native_resolution=True)`, None outside it
         # system.py:91 builds a tracker from the config; here the caller's (`track_image(frames)` per frame of pass 1,
@@ -453,12 +471,29 @@ class SLAMSystem:
         if c.fused_depth_color:
             rgbs = torch.empty((T, V, H0, W0, 3), dtype=torch.uint8, device=self.device)
         xyz = cloud.xyz.contiguous()
+        # `SLAMConfig.complete_depth`: `run` has left the clip's frame maps in `_complete_pred`; the chunk's fused maps are
+        # completed by them right after the resolve - one bits and one complete launch (`ingest.depth_complete`)
+        pred, self._complete_pred, self._complete = getattr(self, "_complete_pred", None), None, None
+        completes = cstats = None
+        if pred is not None:
+            cstats = torch.zeros(4, dtype=torch.int64, device=self.device)
+            if c.complete_depth_sink is None:
+                completes = torch.empty((T, V, H0, W0), dtype=c.frame_depth_dtype, device=self.device)
         for c0 in range(0, T, chunk):
             n = min(chunk, T - c0)
             zbuf = ingest.cloud_zbuffer(n * V, H0, W0, self.device)
             ingest.cloud_render(xyz, cams[c0:c0 + n].view(n * V, 7), b.intrinsics.repeat(n, 1), b.camera_type, geom, zbuf,
                                 cloud.voxel, max_radius=c.fused_depth_max_radius)
             depth, rgb, _ = ingest.cloud_resolve(zbuf, rgb_points, dtype=c.frame_depth_dtype)
+            if pred is not None:
+                done = ingest.depth_complete(depth, pred[c0:c0 + n].view(n * V, H0, W0), K=c.complete_depth_k,
+                                             radius=c.complete_depth_radius, domain="depth",
+                                             wrap_x=b.camera_type == "panorama", stats=cstats,
+                                             out=completes[c0:c0 + n].view(n * V, H0, W0) if completes is not None else None)[0]
+                if c.complete_depth_sink is not None:
+                    for j in range(n):
+                        for v in range(V):
+                            c.complete_depth_sink(c0 + j, v, done[j * V + v])
             if depths is not None:
                 depths[c0:c0 + n] = depth.view(n, V, H0, W0)
             if rgbs is not None:
@@ -467,6 +502,8 @@ class SLAMSystem:
                 for j in range(n):
                     for v in range(V):
                         c.fused_depth_sink(c0 + j, v, depth[j * V + v])
+        if pred is not None:  # the clip's four counters: one read-back
+            self._complete = (completes, dict(zip(("affine", "scale_only", "unreached", "rejected"), cstats.tolist())))
         return depths, rgbs
 
     def _check_camera(self, camera_type, frames, native_resolution):
@@ -488,6 +525,9 @@ class SLAMSystem:
         if self.metric_depth is not None:
             raise ValueError("camera_type='panorama': depth models estimate pinhole depth; the disparities of this "
                              "camera are inverse ranges")
+        if self.config.complete_depth and frames[0][0].rgb.shape[1] < 2 * int(self.config.complete_depth_radius) + 1:
+            raise ValueError("camera_type='panorama' with complete_depth: the frames must be at least "
+                             "2 * complete_depth_radius + 1 columns wide (the search disc may not meet itself round the seam)")
         for f in frames[0]:
             K = f.intrinsics
             if K is None or tuple(K.shape) != (4,) or bool((K != 0).any()):
@@ -547,7 +587,16 @@ class SLAMSystem:
         beside `frame_depths`: that cloud drawn back into every frame and view with the final poses (`FusedCloud.render`'s
         rule: the nearest point whose footprint covers the pixel, 0 where none does) - one surface for the whole clip,
         gated by confidence already - and with `fused_depth_color` `fused_rgb` [T,V,H0,W0,3] uint8; or every map goes to
-        `SLAMConfig.fused_depth_sink` and `fused_depths` stays None.  It only reads."""
+        `SLAMConfig.fused_depth_sink` and `fused_depths` stays None.  It only reads.
+
+        With `SLAMConfig.complete_depth` on top of that, `complete_depths` [T,V,H0,W0] (`frame_depth_dtype`) is the
+        hole-free form of those maps: `fused_depths` bit for bit where they are positive (and the frame has a depth
+        there: both are needed to anchor a fit); elsewhere the frame's own
+        `frame_depths` value, scaled and shifted (in the disparity domain) to agree with the `complete_depth_k` nearest
+        fused pixels within `complete_depth_radius`; 0 only where no fused pixel is in reach or the frame has no depth.
+        `complete_depth_stats` counts the filled pixels by kind.  Or every map goes to `SLAMConfig.complete_depth_sink`
+        and `complete_depths` stays None.  For the panorama the columns are a circle and the frames must be at least
+        2 * `complete_depth_radius` + 1 wide (`ValueError`).  It only reads."""
         frames = [f if isinstance(f, (list, tuple)) else [f] for f in frames]
         total, n_views = len(frames), len(frames[0])
         assert total > 0 and all(len(f) == n_views for f in frames)
@@ -607,6 +656,11 @@ class SLAMSystem:
         if self.config.fused_cloud:
             up.update(fused_cloud=self._extract_cloud())
         if self.config.fused_depth:
+            if self.config.complete_depth:
+                self._complete_pred = up["frame_depths"]
             fused_depths, fused_rgb = self._render_fused_depths(up["fused_cloud"], filled.poses, resizes)
             up.update(fused_depths=fused_depths, fused_rgb=fused_rgb)
+            if self.config.complete_depth:
+                (complete_depths, complete_stats), self._complete = self._complete, None
+                up.update(complete_depths=complete_depths, complete_depth_stats=complete_stats)
         return SLAMOutput(trajectory=filled.poses.inv(), intrinsics=intrinsics, rig=SE3(b.rig.clone()), slam_map=slam_map, **up)
